@@ -10,7 +10,10 @@ when it was not launched by it).  Headline = N independent scan streams, one per
 the ``sharded`` object of the same line is the north-star split measured right after it: ONE stream, registration map and
 mesher sharded by voxel bricks over the ranks (strong scaling) -- see DESIGN.md "Multi-GPU".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and prints the line; everything
+else it can measure -- the CPU baseline, the instrumented legs (`roofline`, `stages_ms_serial`, `kernels_ms_per_scan`), the neighbourhood-size histogram
+and the other BASELINE configurations under `extra` -- runs with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step computed (the
+posterior state and that scan's mesh result lists) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -102,14 +105,29 @@ def build_big_map(h, cfg, torch, dev, target_voxels, side_m, seed=20260924, also
     return nv
 
 
-def livox_scan_torch(torch, dev, k, R, t, n_pts, extT, seed=20260924, range_sigma=0.02, bearing_sigma_deg=0.05, blind=1.0):
-    """synth.livox_scan on the GPU (harness only: the long steady-state leg needs hundreds of scans, the numpy ray caster takes seconds per scan).
-    Same scan model -- Halton(2,3) directions offset per scan, the same procedural world, range / bearing noise -- with torch's generator."""
+def halton_torch(torch, dev, n, base, start=1):
+    """synth.halton on the device: the same integer digits and the same float64 operations in the same order (bit-identical)"""
+    i = torch.arange(start, start + n, device=dev, dtype=torch.int64)
+    f = torch.ones(n, device=dev, dtype=torch.float64)
+    r = torch.zeros(n, device=dev, dtype=torch.float64)
+    v = start + n - 1
+    while v > 0:          # as many rounds as the largest index has digits: synth.halton's `while any(i > 0)`
+        f = f / base
+        r = r + f * (i % base)
+        i = i // base
+        v //= base
+    return r
+
+
+def livox_scan_torch(torch, dev, k, R, t, n_pts, extT, seed=20260924, range_sigma=0.02, bearing_sigma_deg=0.05, blind=1.0, box_chunk=32):
+    """synth.livox_scan on the GPU (harness only: the numpy ray caster takes seconds per scan).  Same scan model -- Halton(2,3) directions offset
+    per scan, the same procedural world, range / bearing noise -- with torch's generator.  The boxes are tested `box_chunk` at a time; the nearest
+    valid hit over all of them is what the box-by-box loop kept."""
     m = int(n_pts * 2.2) + 64
     start = 1 + k * m
-    az = (synth.halton(m, 2, start) - 0.5) * np.deg2rad(70.4)
-    el = (synth.halton(m, 3, start) - 0.5) * np.deg2rad(77.2)
-    dirs = torch.from_numpy(np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)).to(dev)
+    az = (halton_torch(torch, dev, m, 2, start) - 0.5) * np.deg2rad(70.4)
+    el = (halton_torch(torch, dev, m, 3, start) - 0.5) * np.deg2rad(77.2)
+    dirs = torch.stack([torch.cos(el) * torch.cos(az), torch.cos(el) * torch.sin(az), torch.sin(el)], dim=1)
     Rt = torch.from_numpy(np.asarray(R, dtype=np.float64)).to(dev)
     o = np.asarray(R, dtype=np.float64) @ np.asarray(extT, dtype=np.float64) + np.asarray(t, dtype=np.float64)
     d = dirs @ Rt.T
@@ -121,16 +139,19 @@ def livox_scan_torch(torch, dev, k, R, t, n_pts, extT, seed=20260924, range_sigm
     tb = torch.where(ok, tg, tb)
     inv = 1.0 / torch.where(d.abs() < 1e-12, torch.full_like(d, 1e-12), d)
     ci, cj, rc = int(np.floor(o[0] / L)), int(np.floor(o[1] / L)), int(np.ceil(100.0 / L)) + 1
-    ot = torch.from_numpy(o).to(dev)
+    los, his = [], []
     for i in range(ci - rc, ci + rc + 1):
         for j in range(cj - rc, cj + rc + 1):
             lo = np.array([i * L + synth.BOX_LO, j * L + synth.BOX_LO, synth.GROUND_Z]); hi = np.array([i * L + synth.BOX_HI, j * L + synth.BOX_HI, synth.BOX_TOP])
             if np.linalg.norm(0.5 * (lo + hi)[:2] - o[:2]) > 108.0:
                 continue
-            t1 = (torch.from_numpy(lo).to(dev) - ot) * inv; t2 = (torch.from_numpy(hi).to(dev) - ot) * inv
-            tn = torch.minimum(t1, t2).max(dim=1).values; tf = torch.maximum(t1, t2).min(dim=1).values
-            hit = (tn <= tf) & (tn > 0) & (tn < tb)
-            tb = torch.where(hit, tn, tb)
+            los.append(lo - o); his.append(hi - o)
+    lo_o, hi_o = torch.from_numpy(np.array(los)).to(dev), torch.from_numpy(np.array(his)).to(dev)
+    for b in range(0, len(los), box_chunk):
+        t1 = lo_o[None, b:b + box_chunk, :] * inv[:, None, :]; t2 = hi_o[None, b:b + box_chunk, :] * inv[:, None, :]
+        tn = torch.minimum(t1, t2).max(dim=2).values; tf = torch.maximum(t1, t2).min(dim=2).values
+        tn = torch.where((tn <= tf) & (tn > 0), tn, torch.full_like(tn, inf))
+        tb = torch.minimum(tb, tn.min(dim=1).values)
     keep = torch.isfinite(tb) & (tb <= 100.0) & (tb > blind)
     dirs, rg = dirs[keep][:n_pts], tb[keep][:n_pts]
     g = torch.Generator(device=dev); g.manual_seed(seed + 7919 * k)
@@ -171,6 +192,24 @@ def corridor_cloud(torch, dev, n_scans, spacing=0.07, reach=45.0, seed=20260926)
     return torch.cat([P, torch.full((P.shape[0], 1), 50.0, device=dev)], dim=1).contiguous()
 
 
+def host_cpus():
+    """CPUs this process may keep busy: the affinity mask, capped by OMP_NUM_THREADS where the environment sets it (a shared host's budget is smaller
+    than the machine os.cpu_count() reports)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "") or n))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+def scan_cache_dir():
+    """the synthetic scans are generated once per machine and user (a cache another user created is not writable)"""
+    uid = os.getuid() if hasattr(os, "getuid") else 0
+    import tempfile
+    return os.path.join(tempfile.gettempdir(), f"immesh_scan_cache_{uid}")
+
+
 def make_scans(n_scans, n_pts, cfg, cache_dir, kitti=False):
     """Synthetic Livox-shaped stream: raw scans (lidar frame, xyzI) + the VoxelGrid-downsampled clouds.  The numpy ray caster takes
     1-2 s per scan, and the CPU-baseline leg wants >= 220 scans: missing scans are generated by worker PROCESSES (immesh_amd/scan_gen.py, started
@@ -179,7 +218,7 @@ def make_scans(n_scans, n_pts, cfg, cache_dir, kitti=False):
     os.makedirs(cache_dir, exist_ok=True)
     extT = [float(v) for v in cfg.extT]
     missing = [k for k in range(n_scans) if not os.path.exists(scan_gen.scan_path(cache_dir, n_pts, kitti, k)[:-4] + "_down.npy")]
-    nproc = max(1, min(64, (os.cpu_count() or 1) - 2, len(missing)))
+    nproc = max(1, min(64, host_cpus(), len(missing)))
     if nproc > 1 and len(missing) > 4:
         env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1", MKL_NUM_THREADS="1")
         procs = [subprocess.Popen([sys.executable, "-m", "immesh_amd.scan_gen", cache_dir, str(n_pts), str(int(kitti))] + [repr(v) for v in extT] + [str(k) for k in missing[w::nproc]],
@@ -272,6 +311,23 @@ def roofline_from_committed_profile(mesh, cnt, n_scans, n_raw, note):
     return None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, seed=20261016):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float32 / 8-bit sources) or float64 (everything else: integer ids are exact
+    there).  Over DUMP_BUDGET_BYTES in all, every array keeps the same fixed, seeded sample of its rows (a fraction of them, in their order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {n: np.ascontiguousarray(a, dtype=np.float32 if a.dtype in (np.float32, np.uint8, np.int8) else np.float64) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    for n, a in conv.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_BUDGET_BYTES / total))
+            a = a[np.sort(np.random.default_rng(seed).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {sorted(conv)}")
+
+
 COUNTER_KEYS = ("n_iter", "n_match", "n_plane_tests", "n_extra_probe", "n_refits", "n_refit_pts", "n_app", "n_new", "c1", "v_act", "n_v", "c20", "n_u", "t_v", "t_add", "t_rem")
 
 
@@ -295,23 +351,26 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
     comm = "none"
     if sharded:
         comm = D.attach_collectives(h, hip, dist, args.backend, dev, world, bool(args.mesh))
-    n_extra = (2 * args.profile_scans if full else 0) + (args.nu_scans if args.mesh else 0)
+    n_extra = (2 * args.profile_scans + (args.nu_scans if args.mesh else 0)) if full else 0
     n_pre = max(0, args.map_scans - 1) if kitti else 0      # C4: scans 1 .. map_scans-1 build the map before the warm-up
     n_total = n_pre + args.warmup + args.steps + n_extra
-    n_cpu = int(min(260, 24 + args.cpu_seconds * 12)) if (full and args.cpu_seconds > 0 and rank == 0 and not args.gpu_scans) else 0   # the CPU-baseline leg replays the stream from scan 1: 20 + 200 + the all-cores sample
+    n_cpu = int(min(260, 24 + args.cpu_seconds * 12)) if (full and args.cpu_seconds > 0 and rank == 0) else 0   # the CPU-baseline leg replays the stream from scan 1: 20 + 200 + the all-cores sample
     n_cpu += n_pre if n_cpu else 0
     extT_np = np.array(list(cfg.extT))
+    n_gen = max(n_total + 1 + (world - 1), n_cpu)
+    dev_raws = None
     if args.gpu_scans and not kitti:
-        # scans ray-cast on the GPU (harness), down-sampled by the library's own VoxelGrid BEFORE the timed region: the long steady-state leg
-        raws, downs, d_raw, d_down = [], [], [], []
-        for kk in range(n_total + 1):
+        # scans ray-cast on the GPU (harness), down-sampled by the library's own VoxelGrid BEFORE the timed region: milliseconds per scan, so the
+        # set-up does not grow with --steps the way the host ray caster's seconds per scan did; host copies for the legs that take host clouds
+        raws, downs, dev_raws = [], [], []
+        for kk in range(n_gen):
             Rk, tk = synth.trajectory_pose(kk)
             r = livox_scan_torch(torch, dev, kk, Rk, tk, args.pts, extT_np)
             dn, _ = h.downsample(r.data_ptr(), 0.4, n=r.shape[0], stride=4, to_host=True)
-            d_raw.append(r); d_down.append(torch.from_numpy(dn).to(dev)); raws.append(np.empty((r.shape[0], 0))); downs.append(dn)
+            dev_raws.append(r); raws.append(r.cpu().numpy()); downs.append(dn)
     else:
-        raws, downs = make_scans(max(n_total + 1 + (world - 1), n_cpu), args.pts, cfg, os.path.join(os.environ.get("TMPDIR", "/tmp"), "immesh_scan_cache"), kitti)
-        cpu_raws, cpu_downs = raws, downs
+        raws, downs = make_scans(n_gen, args.pts, cfg, scan_cache_dir(), kitti)
+    cpu_raws, cpu_downs = raws, downs
     if kitti:   # the map grows from the stream itself (3 m root voxels, max_layer 4)
         R0_, t0_ = synth.trajectory_pose(0)
         h.map_build(np.ascontiguousarray(raws[0][:, :3]), capi.make_state(R=R0_, t=t0_))
@@ -319,10 +378,9 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
     else:
         n_map = build_big_map(h, cfg, torch, dev, args.map_voxels, side)
     idx = D.stream_of_rank(0 if sharded else rank, n_total)   # replicas: rank r replays the stream phase-shifted by r scans; sharded: one stream
-    if not (args.gpu_scans and not kitti):
-        raws, downs = [raws[i] for i in idx], [downs[i] for i in idx]
-        d_raw = [torch.from_numpy(r).to(dev) for r in raws]
-        d_down = [torch.from_numpy(d).to(dev) for d in downs]
+    raws, downs = [raws[i] for i in idx], [downs[i] for i in idx]
+    d_raw = [dev_raws[i] for i in idx] if dev_raws is not None else [torch.from_numpy(r).to(dev) for r in raws]
+    d_down = [torch.from_numpy(d).to(dev) for d in downs]
     n_ds_mean = float(np.mean([len(d) for d in downs[1 + n_pre:1 + n_pre + args.warmup + args.steps]]))
     mesh_seed, seed_cloud = None, None
     if args.dense_mesh and args.mesh and not kitti and not sharded:
@@ -391,12 +449,12 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
         log(f"[bench] C4 map: {n_pre + 1} scans -> {n_map} root voxels, {h.counters()['n_vertices']} mesh vertices ({time.time() - t_pre:.1f} s)")
     if args.dropin_shim:
         # ---- the same stream THROUGH THE DROP-IN: two threads as the reference runs them, host clouds, lists fetched, mirrors applied
-        # the host mirror behind the shim: the REFERENCE'S OWN Triangle_manager (drop_in/_ref/libimmesh_dropin_async_refmirror.so: triangle.hpp / .cpp compiled from
+        # the host mirror behind the shim: the REFERENCE'S OWN Triangle_manager (oracle/_ref/libimmesh_dropin_async_refmirror.so: triangle.hpp / .cpp compiled from
         # where they lie, built where /root/reference exists and carried to the GPU box) when it is there, else the hash-map stand-in of drop_in/stubs
-        ref_so = os.path.join(ROOT, "drop_in", "_ref", "libimmesh_dropin_async_refmirror.so")
+        ref_so = os.path.join(ROOT, "oracle", "_ref", "libimmesh_dropin_async_refmirror.so")
         use_ref = args.dropin_mirror == "ref" or (args.dropin_mirror == "auto" and os.path.exists(ref_so))
         if use_ref and not os.path.exists(ref_so):
-            raise SystemExit("--dropin-mirror ref: drop_in/_ref/libimmesh_dropin_async_refmirror.so is not built (make -C drop_in refmirror, needs /root/reference)")
+            raise SystemExit("--dropin-mirror ref: oracle/_ref/libimmesh_dropin_async_refmirror.so is not built (make -C drop_in refmirror, needs the reference tree: REF=...)")
         if not use_ref:
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "drop_in"), "libimmesh_dropin_async.so"], stdout=subprocess.DEVNULL)
         sl = ctypes.CDLL(ref_so if use_ref else os.path.join(ROOT, "drop_in", "libimmesh_dropin_async.so"))
@@ -444,6 +502,8 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
         D.barrier()
         elapsed = D.max_over_ranks(float(ms[1]) * 1e-3, dev)
         t_marks = []
+        if args.dump_outputs and rank == 0:
+            write_outputs(args.dump_outputs, {"state": st})
     else:
         # (before the warm-up, not between it and the timed region: a generation-2 collection of the harness's objects inside the loop is a 30 ms stall
         #  -- seen: one call of 32 ms among 50 of 0.25 ms --, and tens of milliseconds of idle device in front of the first timed scan cost that scan
@@ -476,9 +536,16 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
                 f"enqueue of the next (immesh_downsample_begin) {1e3 * ds_state['begin_s'] / ds_state['calls']:.4f}")
         D.barrier()
         elapsed = D.max_over_ranks(time.perf_counter() - t_begin, dev)
+        if args.dump_outputs and rank == 0:
+            outs = {"state": st, "scan_info": np.array([info["n_iter"], info["n_match"]], np.float64)}
+            if mesh_mode & 3:   # the last timed scan's job is the newest one: mesh_wait / the serial call made it current
+                mf = h.mesh_fetch()
+                outs.update({kk_: v for kk_, v in mf.items() if isinstance(v, np.ndarray)})
+                outs["mesh_counts"] = np.array([mf["vtx_base"], mf["n_voxels_meshed"]], np.float64)
+            write_outputs(args.dump_outputs, outs)
     cnt = h.counters()
     nu_hist = None
-    if (mesh_mode & 3) and args.nu_scans > 0 and not sharded:
+    if full and (mesh_mode & 3) and args.nu_scans > 0 and not sharded:
         # neighbourhood sizes of the scans right after the timed region (serial): which triangulation kernel takes which share of the voxels
         sizes = []
         for _ in range(args.nu_scans):
@@ -498,7 +565,7 @@ def measure(args, torch, D, dist, hip, rank, world, local, dev, sharded, full):
            "pose_err": float(np.linalg.norm(st[9:12] - synth.trajectory_pose(idx[k - 1])[1])),
            "scan_thread_ms": ({"p50": round(float(np.percentile(np.diff(t_marks) * 1e3, 50)), 4), "p95": round(float(np.percentile(np.diff(t_marks) * 1e3, 95)), 4)}
                               if len(t_marks) > 2 else None),   # host time per immesh_process_scan call (asynchronous mode: until the pose is final)
-           "cpu_inputs": (cfg, cpu_raws, cpu_downs, R0, t0, seed_cloud) if not (args.gpu_scans and not kitti) else None}
+           "cpu_inputs": (cfg, cpu_raws, cpu_downs, R0, t0, seed_cloud)}
     if sharded:
         res["shard_traffic"] = h.shard_traffic()
         if rank == 0 and not kitti:
@@ -818,8 +885,8 @@ def main():
     ap.add_argument("--dropin-shim", type=int, default=0, help="1 = the timed region runs THROUGH THE DROP-IN (drop_in/immesh_shim_async.cpp behind drop_in/dropin_driver.cpp): pcl-shaped host clouds in, "
                     "one immesh_process_scan(ASYNC) per scan on the scan thread, every frame's result lists fetched and applied to the Global_map / Triangle_manager mirrors by the service thread")
     ap.add_argument("--async-mesh", type=int, default=1, help="1 = meshing of scan k overlaps registration of scan k+1 (the reference's mesh service thread); 0 = strictly serial per scan")
-    ap.add_argument("--gpu-scans", type=int, default=0, help="1 = the scan stream is ray-cast on the GPU by the harness (torch) and down-sampled by the library before the timed region: "
-                    "hundreds of scans in seconds (the steady-state leg); the CPU-baseline leg needs the default host-generated stream")
+    ap.add_argument("--gpu-scans", type=int, default=1, help="1 (default) = the avia scan stream is ray-cast on the GPU by the harness (torch) and down-sampled by the library before "
+                    "the timed region: milliseconds per scan; 0 = the numpy ray caster (seconds per scan, cached under the temporary directory).  --config velodyne always uses the numpy one")
     ap.add_argument("--dense-mesh", type=int, default=1, help="1 (default, SURVEY 8(d) C3: \"mesh map pre-seeded from the same survey, capped at the corridor\") = the MESH map is pre-seeded from a dense "
                     "survey of the stream's corridor before the stream starts; 0 = seeded by scan 0 only (the stream meshes unexplored ground: the headline of rounds 1-2)")
     ap.add_argument("--nu-scans", type=int, default=5, help="scans after the timed region whose per-voxel neighbourhood sizes n_u are collected (histogram + kernel shares)")
@@ -834,11 +901,15 @@ def main():
     ap.add_argument("--sharded-leg", type=int, default=1, help="N>1: after the replica headline also measure the sharded split (ONE stream over N ranks) and report it as `sharded`")
     ap.add_argument("--shard-scheme", type=int, default=0, choices=[0, 1], help="brick ownership of the sharded map / mesher: 0 = lattice colouring (bx + 3 by + 5 bz) mod W (default), 1 = hash(brick) mod W (rounds 1-4)")
     ap.add_argument("--dropin-mirror", choices=["auto", "ref", "stub"], default="auto", help="--dropin-shim 1: the host mirror the shim applies the lists to: ref = the reference's own Triangle_manager "
-                    "(drop_in/_ref/libimmesh_dropin_async_refmirror.so), stub = the stand-in of drop_in/stubs, auto = ref when it is built")
+                    "(oracle/_ref/libimmesh_dropin_async_refmirror.so), stub = the stand-in of drop_in/stubs, auto = ref when it is built")
     ap.add_argument("--map-scans", type=int, default=50, help="--config velodyne (BASELINE configs[3] = SURVEY 8(d) C4): the map -- registration map AND mesh map -- is built from the first "
                     "this many scans of the stream (scan 0 through immesh_map_build, the rest through the full pipeline, untimed), then the stream is timed; 1 = scan 0 only (the variant of rounds 1-4)")
-    ap.add_argument("--extra-configs", type=int, default=-1, help="1 = also run BASELINE configs[1] (--mesh 0) and configs[3] (--config velodyne) as short child runs and report them under "
-                    "`extra`; default: on for the plain N=1 headline run")
+    ap.add_argument("--extra-configs", type=int, default=-1, help="--full only: 1 = also run BASELINE configs[1] (--mesh 0) and configs[3] (--config velodyne) as short child runs and "
+                    "report them under `extra`; default: on for the N=1 headline workload")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: the CPU baseline, the instrumented legs (roofline, serial stage times, "
+                    "per-kernel times), the neighbourhood-size histogram and the other configurations (`extra`).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed (posterior state, that scan's mesh result "
+                    "lists) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -864,7 +935,7 @@ def main():
     if args.dry_run_rank >= 0 or args.dry_run_rank == -2:
         return dry_run_leg(args, torch, hip, dev, local)
 
-    res = measure(args, torch, D, dist, hip, rank, world, local, dev, sharded=only_sharded, full=True)
+    res = measure(args, torch, D, dist, hip, rank, world, local, dev, sharded=only_sharded, full=args.full)
     value = D.aggregate_throughput(args.steps, 1 if only_sharded else world, res["elapsed"])
     mesh_mode, cnt = res["mesh_mode"], res["cnt"]
     cnt["_n_ds_mean"] = res["n_ds_mean"]
@@ -945,7 +1016,7 @@ def main():
             out["exchange_calls_per_scan"] = round(res["shard_traffic"]["calls"] / max(1, args.steps + args.warmup + 1), 2)
         if res.get("load_balance"):
             out["load_balance_point_share_per_brick_size"] = res["load_balance"]
-        if args.profile_scans > 0:   # until the live leg has delivered: the committed rocprofv3 average of the dominant kernel with this run's own counters
+        if args.full and args.profile_scans > 0:   # until the live leg has delivered: the committed rocprofv3 average of the dominant kernel with this run's own counters
             out["roofline"] = add_traffic(roofline_from_committed_profile(args.mesh, cnt, args.steps, args.pts, "not run yet"))
     threading.Thread(target=watchdog, daemon=True).start()
 
@@ -959,7 +1030,7 @@ def main():
             live = build_roofline(res, args)
             if live is not None:
                 out["roofline"] = add_traffic(live)
-        elif args.profile_scans > 0:
+        elif args.full and args.profile_scans > 0:
             out["roofline"] = add_traffic(roofline_from_committed_profile(args.mesh, cnt, args.steps, args.pts, prof_note or "the HIP-event leg did not run"))
         if prof_note:
             out["profile_leg_note"] = prof_note
@@ -978,7 +1049,7 @@ def main():
                                                                        "TORCHELASTIC_MAX_RESTARTS", "TORCHELASTIC_USE_AGENT_STORE", "TORCH_NCCL_ASYNC_ERROR_HANDLING")}
         cmd = [sys.executable, os.path.abspath(sys.argv[0]), "--gpus", str(world), "--shard", "1", "--backend", args.backend, "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--pts", str(args.pts), "--map-voxels", str(args.map_voxels), "--mesh", str(args.mesh), "--config", args.config, "--cpu-seconds", "0", "--profile-scans", "0",
-               "--extra-configs", "0", "--brick-log2", str(args.brick_log2)]
+               "--extra-configs", "0", "--brick-log2", str(args.brick_log2)] + (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         try:
             r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1.5 * args.profile_timeout, text=True)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1005,13 +1076,13 @@ def main():
             out["sharded"] = {"error": str(e)[:200]}
 
     # ---- CPU baseline leg (rank 0, N = 1 semantics: the oracle on this box's host cores)
-    if rank == 0 and args.cpu_seconds > 0 and not args.gpu_scans and world == 1:
+    if rank == 0 and args.full and args.cpu_seconds > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline_leg(args, res["cpu_inputs"], args.cpu_seconds)
-    elif rank == 0 and world > 1:
+    elif rank == 0 and args.full and world > 1:
         out["cpu_baseline_note"] = "timed at N = 1 only (the same host cores, the same oracle: nothing about it changes with the number of GPUs)"
 
     # ---- BASELINE configs[1] and configs[3] as short child runs of this script (N = 1 headline runs only)
-    want_extra = args.extra_configs if args.extra_configs >= 0 else int(world == 1 and args.mesh == 1 and args.config == "avia" and not args.device_downsample and args.pts == 100000 and args.map_voxels >= 10e6)
+    want_extra = args.full and (args.extra_configs if args.extra_configs >= 0 else int(world == 1 and args.mesh == 1 and args.config == "avia" and not args.device_downsample and args.pts == 100000 and args.map_voxels >= 10e6))
     if rank == 0 and want_extra:
         extra = {}
         env = {kk_: v for kk_, v in os.environ.items() if kk_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -1024,7 +1095,7 @@ def main():
                              ("full pipeline, mesh map seeded by scan 0 only (the stream meshes unexplored ground: the headline of rounds 1-2)", ["--dense-mesh", "0"]),
                              ("full pipeline, steady state: 500 scans after 20 warm-up scans", ["--gpu-scans", "1", "--steps", "500", "--warmup", "20", "--nu-scans", "0"]),
                              ("configs[4] dry run: every rank of 8 in turn, alone, 500k-pt scans, 50 M-voxel survey, collectives stubbed (the job waits for the slowest)", ["--dry-run-rank", "-2", "--pts", "500000", "--map-voxels", "50e6", "--steps", "10", "--warmup", "3"])):
-            cmd = [sys.executable, os.path.abspath(sys.argv[0]), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--cpu-seconds", "0", "--profile-scans", "0", "--extra-configs", "0"] + flags   # (later flags win)
+            cmd = [sys.executable, os.path.abspath(sys.argv[0]), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--cpu-seconds", "0", "--profile-scans", "0", "--extra-configs", "0", "--full"] + flags   # (later flags win)
             try:
                 # (IMMESH_DEBUG_WAITS: the library prints, when the context is destroyed, the kernel-entry times of the mesher's last jobs, the job-to-job period
                 #  and how long the scan thread stood waiting for a world buffer -- who paces the pipeline; two getenv calls and one clock read per scan)

@@ -2,6 +2,7 @@
 // replaced bodies.  Input file (little endian): int32 n_scans; per scan: int32 n_raw, int32 n_ds, double prior[348], float raw[n_raw*4]
 // (x y z intensity, body frame), float down[n_ds*3].  Scan 0 initialises the map (voxel_map_init) with state = prior.  Output file: per scan
 // double state[348], int32 effct_feat_num, int32 n_vertices, int32 n_live_triangles, uint64 order-independent hash of the live (triplet, flip) set.
+// The mesh is saved (save_to_ply_file) to the optional third argument, by default <out>.ply.
 #include "immesh_ref_shapes.hpp"
 #include <cstdio>
 #include <cstring>
@@ -13,7 +14,7 @@ static void load_state(const double* o, StatesGroup& s) {
     for (int r = 0; r < 18; r++) for (int c = 0; c < 18; c++) s.cov(r, c) = o[24 + r * 18 + c];
 }
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: shim_main <in> <out>\n"); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: shim_main <in> <out> [<ply>]\n"); return 2; }
     FILE* fi = std::fopen(argv[1], "rb"); FILE* fo = std::fopen(argv[2], "wb");
     if (!fi || !fo) return 2;
     Voxel_mapping vm;
@@ -48,6 +49,6 @@ int main(int argc, char** argv) {
         std::fwrite(st, 8, 348, fo); std::fwrite(&eff, 4, 1, fo); std::fwrite(&nv, 4, 1, fo); std::fwrite(&nl, 4, 1, fo); std::fwrite(&h, 8, 1, fo);
     }
     std::fclose(fi); std::fclose(fo);
-    save_to_ply_file("/tmp/immesh_dropin_test.ply", 0.0, 20);
+    save_to_ply_file(argc > 3 ? std::string(argv[3]) : std::string(argv[2]) + ".ply", 0.0, 20);
     return 0;
 }

@@ -1,5 +1,6 @@
 """bench.py's control flow on CPU (tests/bench_cpu_shim.py stands the oracle in for the HIP library): the one JSON line, the instrumented legs on the
-same context, the fallbacks when they fail or hang (the bench line must survive), the N > 1 launch contract and `--gpus N` spawning its ranks."""
+same context (--full), the fallbacks when they fail or hang (the bench line must survive), the N > 1 launch contract and `--gpus N` spawning its ranks,
+the plain run without the legs and --dump-outputs."""
 import json
 import os
 import subprocess
@@ -7,15 +8,16 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "tests", "bench_cpu_shim.py")
-ARGS = ["--pts", "6000", "--steps", "3", "--warmup", "1", "--profile-scans", "1", "--cpu-seconds", "0.3", "--map-voxels", "1000"]
+PLAIN = ["--pts", "6000", "--steps", "3", "--warmup", "1", "--profile-scans", "1", "--cpu-seconds", "0.3", "--map-voxels", "1000"]
+ARGS = PLAIN + ["--full"]
 
 
-def _run(script, extra=(), env=None, timeout=600):
+def _run(script, extra=(), env=None, timeout=600, args=ARGS):
     e = dict(os.environ)
     e["TMPDIR"] = e.get("TMPDIR", "/tmp")
     if env:
         e.update(env)
-    r = subprocess.run([sys.executable, script] + ARGS + list(extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, env=e, cwd=ROOT)
+    r = subprocess.run([sys.executable, script] + args + list(extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, env=e, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
     return json.loads(lines[0])
@@ -96,6 +98,36 @@ def test_two_rank_replicas_gloo():
     assert abs(d["value"] - 2 * d["steps"] / (d["ms_per_step"] * d["steps"] / 1e3)) < 1e-2 * d["value"]      # whole-job throughput = all ranks' scans / slowest rank's time
 
 
+def test_plain_run_is_the_headline_alone():
+    """without --full: set up, warm up, time the steps, print the line -- no CPU baseline, no instrumented legs, no other configurations"""
+    d = _run(SHIM, args=PLAIN)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in d, k
+    assert d["value"] > 0 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "scans/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["cpu_baseline"] is None and d["roofline"] is None and d["stages_ms_serial"] is None and d["n_u"] is None and not d["kernels_ms_per_scan"]
+    assert "extra" not in d and "profile_leg_note" not in d
+
+
+def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the last timed scan's posterior state and mesh result lists as .npy (float32 / float64); the same arguments give the same files"""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d_ = tmp_path / f"run{i}"
+        d = _run(SHIM, ["--dump-outputs", str(d_)], args=PLAIN)
+        assert d["value"] > 0
+        runs.append({f[:-4]: np.load(d_ / f) for f in sorted(os.listdir(d_))})
+    a, b = runs
+    assert {"state", "scan_info", "new_vtx", "tri_add", "tri_rem", "tri_upd", "flip_add", "smooth_ids", "smooth_xyz", "mesh_counts"} <= set(a)
+    assert a["state"].dtype == np.float64 and a["state"].shape == (348,) and np.isfinite(a["state"]).all()
+    assert a["scan_info"][0] >= 1 and a["scan_info"][1] > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(v, b[k], err_msg=k)
+
+
 def test_kernel_source_fingerprint_ignores_comments_and_the_committed_traffic_file_is_current(tmp_path, monkeypatch):
     """roofline.traffic is only reported from a PMC file measured on THESE kernel sources (bench.kernel_sources_sha: the compiled text, comments and
     layout removed).  A comment or blank line must not move the fingerprint, a token must; and the file under profiles/ should be the current one
@@ -129,3 +161,14 @@ def test_kernel_source_fingerprint_ignores_comments_and_the_committed_traffic_fi
     meta = json.load(open(os.path.join(ROOT, "profiles", bench.COMMITTED_TRAFFIC)))["_meta"]
     if meta["kernel_sources_sha16"] != base:
         pytest.skip(f"profiles/{bench.COMMITTED_TRAFFIC} was measured on {meta['kernel_sources_sha16']}, the kernels are {base}: tools/r04_traffic.sh regenerates it")
+
+
+def test_device_halton_is_the_host_sequence():
+    """the scan stream's Halton directions on the device (bench.halton_torch) are synth.halton's, bit for bit"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from immesh_amd import synth
+    for base, start in ((2, 1), (3, 1), (2, 1 + 999 * 220064), (3, 1 + 999 * 220064)):
+        np.testing.assert_array_equal(bench.halton_torch(torch, torch.device("cpu"), 5000, base, start).numpy(), synth.halton(5000, base, start))

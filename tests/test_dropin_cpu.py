@@ -4,6 +4,8 @@ issued directly -- and `make -C drop_in shim_main` (the product link against lib
 import os
 import subprocess
 
+import pytest
+
 from conftest import make_oracle, ROOT
 from test_gpu_dropin import run_drop_in, run_drop_in_async
 

@@ -120,20 +120,22 @@ def run_drop_in(oracle_lib, make_direct, target, tmp_path, expect_ply=True):
             assert got[k]["nv"] == nv and got[k]["nl"] == len(live) and int(got[k]["hash"]) == _live_hash(live), k
     assert got[1]["nv"] > 500 and got[-1]["nl"] > 3000
     if expect_ply:
-        assert os.path.getsize("/tmp/immesh_dropin_test.ply") > 10000       # save_to_ply_file through the shim
+        assert os.path.getsize(fout + ".ply") > 10000       # save_to_ply_file through the shim
 
 
 # ---- the SERVICE-LEVEL (asynchronous) drop-in: drop_in/immesh_shim_async.cpp behind drop_in/dropin_driver.cpp (two threads, as the reference runs them) ----------
 def _dropin_lib(name):
     import ctypes as C
-    if name.startswith("_ref/"):   # the variants with the reference's own Triangle_manager as the host mirror: built only where /root/reference exists
+    path = os.path.join(ROOT, "drop_in", name)
+    if name.startswith("_ref/"):   # the variants with the reference's own Triangle_manager as the host mirror: built into oracle/_ref only where the reference tree exists
+        path = os.path.join(ROOT, "oracle", name)
         if os.path.exists("/root/reference/src/meshing/r3live/triangle.hpp"):
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "drop_in"), "refmirror"])
-        elif not os.path.exists(os.path.join(ROOT, "drop_in", name)):
-            pytest.skip(f"drop_in/{name} not built and /root/reference absent")
+        elif not os.path.exists(path):
+            pytest.skip(f"oracle/{name} not built and the reference tree absent")
     else:
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "drop_in"), name])
-    lib = C.CDLL(os.path.join(ROOT, "drop_in", name))
+    lib = C.CDLL(path)
     lib.dropin_create.restype = C.c_void_p; lib.dropin_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.dropin_destroy.argtypes = [C.c_void_p, C.c_int]
     lib.dropin_first_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

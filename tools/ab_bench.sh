@@ -2,7 +2,7 @@
 # A/B on ONE box: bench.py under different environment switches (and, if present, against a library built from another commit).
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
-one() { timeout 80 python $R/bench.py --cpu-seconds 0 --extra-configs 0 2>/dev/null | python -c "
+one() { timeout 80 python $R/bench.py --full --cpu-seconds 0 --extra-configs 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1', d['value'], d['stages_ms_serial'], d['scan_thread_ms']); print('   ', {k.split('(')[0][:24]: v for k, v in d['kernels_ms_per_scan'].items() if v > 0.012})"; }
 one base
