@@ -837,14 +837,43 @@ int immesh_decode_livox(immesh_ctx* c, const uint8_t* wire, int32_t n, int32_t n
     launch_decode_livox_emit(s, (const uint8_t*)d_in, n, keep, pos, c->d_und_in, c->p_nseg);
     return decode_finish(c, n, out_xyzit, n_out);
 }
+// velodyne_handler's elevation gates as a function of the float q = z / sqrtf(x*x + y*y), in the reference's own expression (host glibc atanf)
+static bool velodyne_keep_q(float q, int n_scans) {
+    const float angle = (float)((double)(std::atan(q) * 180) / M_PI);
+    if (std::isnan(angle)) return false;   // (the reference's int(NaN) is INT_MIN on x86-64: scan_id < 0)
+    int scan_id;
+    if (angle >= -8.83) scan_id = int((2 - angle) * 3.0 + 0.5);
+    else scan_id = n_scans / 2 + int((-8.83 - angle) * 2.0 + 0.5);
+    return !(angle > 2 || angle < -24.33 || scan_id > 50 || scan_id < 0);
+}
+// Float <-> integer in the order of the values (-0.0 and +0.0 share 0), -0x7f800000 (-inf) .. 0x7f800000 (+inf).
+static int32_t f32_ordered(float f) { uint32_t b; std::memcpy(&b, &f, 4); return (b & 0x80000000u) ? -(int32_t)(b & 0x7fffffffu) : (int32_t)b; }
+static float ordered_f32(int32_t k) { const uint32_t b = k < 0 ? (0x80000000u | (uint32_t)(-k)) : (uint32_t)k; float f; std::memcpy(&f, &b, 4); return f; }
+// The kept points are exactly those with q_lo <= q <= q_hi.  This rests on angle(q) being monotone non-decreasing in q, i.e. on glibc's atanf
+// being monotone: then the gates (angle <= 2, angle >= -24.33, and below -8.83 a scan_id that grows as the angle falls, cut at 50) keep one
+// interval of angles, hence one interval of q.  An enumeration of all 2^32 floats q with glibc 2.35's atanf found exactly one such interval for
+// n_scans 16, 32 and 64 (q_lo 0xbee77fec / 0xbea7264c, q_hi 0x3d0f0915).  q = 0 (angle 0, scan_id 6) is kept for every n_scans >= 1, so each
+// end is found by a bisection over the ordered float bit patterns on its side of 0: about 2 x 31 atanf calls.  For n_scans / 2 >= 51 the lower
+// branch is cut entirely and q_lo falls on the -8.83 degree boundary by itself.
+static void velodyne_q_interval(int n_scans, float* q_lo, float* q_hi) {
+    int32_t dropped = f32_ordered(-INFINITY), kept = 0;   // angle -90: dropped
+    while (kept - dropped > 1) { const int32_t m = dropped + (kept - dropped) / 2; (velodyne_keep_q(ordered_f32(m), n_scans) ? kept : dropped) = m; }
+    *q_lo = ordered_f32(kept);
+    kept = 0; dropped = f32_ordered(INFINITY);             // angle +90: dropped
+    while (dropped - kept > 1) { const int32_t m = kept + (dropped - kept) / 2; (velodyne_keep_q(ordered_f32(m), n_scans) ? kept : dropped) = m; }
+    *q_hi = ordered_f32(kept);
+}
 // Preprocess::velodyne_handler   src/preprocess.cpp:497-526
 int immesh_decode_velodyne(immesh_ctx* c, const uint8_t* data, int32_t n, int32_t point_step, int32_t off_x, int32_t off_y, int32_t off_z, int32_t off_intensity,
                            int32_t n_scans, float* out_xyzit, int32_t* n_out) {
     const int32_t mx = std::max(std::max(off_x, off_y), std::max(off_z, off_intensity));
-    if (!c || !data || n <= 0 || n > c->cap_scan || point_step < 16 || point_step > 64 || std::min(std::min(off_x, off_y), std::min(off_z, off_intensity)) < 0 || mx + 4 > point_step) {
-        if (c) c->err = "bad arguments (point_step 16..64, float32 fields inside the point)";
+    if (!c || !data || n <= 0 || n > c->cap_scan || point_step < 16 || point_step > 64 || std::min(std::min(off_x, off_y), std::min(off_z, off_intensity)) < 0 || mx + 4 > point_step ||
+        n_scans <= 0) {
+        if (c) c->err = "bad arguments (point_step 16..64, float32 fields inside the point, n_scans >= 1)";
         return IMMESH_E_INVAL;
     }
+    float q_lo, q_hi;
+    velodyne_q_interval(n_scans, &q_lo, &q_hi);
     (void)hipSetDevice(c->cfg.device);
     ProfBind _pb(c);
     hipStream_t s = c->stream_pre;
@@ -853,7 +882,7 @@ int immesh_decode_velodyne(immesh_ctx* c, const uint8_t* data, int32_t n, int32_
     if (!c->d_raw_stage && (rc = c->dalloc(&c->d_raw_stage, (size_t)c->cap_scan * 64))) return rc;
     if ((rc = pre_resolve(c, data, (size_t)n * point_step, c->d_raw_stage, &d_in))) return rc;
     int32_t* keep = c->p_idx_c; int32_t* pos = c->p_seg;
-    launch_decode_velodyne_keep(s, (const uint8_t*)d_in, n, point_step, off_x, off_y, off_z, n_scans, keep);
+    launch_decode_velodyne_keep(s, (const uint8_t*)d_in, n, point_step, off_x, off_y, off_z, q_lo, q_hi, keep);
     exclusive_sum_i32(s, c->p_sort_temp, c->sort_temp_bytes, keep, pos, n);
     PRE_OUTPUT_FENCE(c);
     launch_decode_velodyne_emit(s, (const uint8_t*)d_in, n, point_step, off_x, off_y, off_z, off_intensity, keep, pos, c->d_und_in, c->p_nseg);

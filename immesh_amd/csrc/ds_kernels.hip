@@ -452,7 +452,8 @@ void kprof_spin(hipStream_t s) { hipLaunchKernelGGL(kprof_spin_kernel, dim3(1), 
 __global__ void undistort_keys_kernel(const float* __restrict__ pts5, int n, uint32_t* __restrict__ key, int32_t* __restrict__ idx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t b = __float_as_uint(pts5[(size_t)i * 5 + 4]);
+    uint32_t b = __float_as_uint(pts5[(size_t)i * 5 + 4]);
+    if (b == 0x80000000u) b = 0u;                           // -0.0 == +0.0: equal stamps keep their arrival order (the checker's stable_sort with <)
     key[i] = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // order-preserving map of float to uint (ascending offset time)
     idx[i] = i;
 }
@@ -551,16 +552,16 @@ __global__ void decode_livox_emit_kernel(const uint8_t* __restrict__ w, int n, c
     }
     if (i == n - 1) *n_out = pos[i] + keep_flag[i];
 }
-__global__ void decode_velodyne_keep_kernel(const uint8_t* __restrict__ d, int n, int step, int ox, int oy, int oz, int n_scans, int32_t* __restrict__ keep) {
+// the elevation gates as one interval of q = z / sqrtf(x*x + y*y) (velodyne_q_interval in c_api.cpp): the product, the correctly rounded
+// sqrtf and division (-ffp-contract=off) give the host's q bit for bit, so no device arctangent decides a point.  A NaN q fails both comparisons.
+__global__ void decode_velodyne_keep_kernel(const uint8_t* __restrict__ d, int n, int step, int ox, int oy, int oz, float q_lo, float q_hi,
+                                            int32_t* __restrict__ keep) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint8_t* p = d + (size_t)i * step;
     const float x = rd_f32(p + ox), y = rd_f32(p + oy), z = rd_f32(p + oz);
-    const float angle = (float)((double)(atanf(z / sqrtf(x * x + y * y)) * 180) / 3.14159265358979323846);
-    int scan_id;
-    if ((double)angle >= -8.83) scan_id = (int)((2 - (double)angle) * 3.0 + 0.5);
-    else scan_id = n_scans / 2 + (int)((-8.83 - (double)angle) * 2.0 + 0.5);
-    keep[i] = ((double)angle > 2 || (double)angle < -24.33 || scan_id > 50 || scan_id < 0) ? 0 : 1;
+    const float q = z / sqrtf(x * x + y * y);
+    keep[i] = (q >= q_lo && q <= q_hi) ? 1 : 0;
 }
 __global__ void decode_velodyne_emit_kernel(const uint8_t* __restrict__ d, int n, int step, int ox, int oy, int oz, int oi, const int32_t* __restrict__ keep_flag,
                                             const int32_t* __restrict__ pos, float* __restrict__ out, int32_t* __restrict__ n_out) {
@@ -582,8 +583,8 @@ void launch_decode_livox_keep(hipStream_t s, const uint8_t* w, int n, int n_scan
 void launch_decode_livox_emit(hipStream_t s, const uint8_t* w, int n, const int32_t* keep, const int32_t* pos, float* out, int32_t* n_out) {
     KLAUNCH(decode_livox_emit_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, n, keep, pos, out, n_out);
 }
-void launch_decode_velodyne_keep(hipStream_t s, const uint8_t* d, int n, int step, int ox, int oy, int oz, int n_scans, int32_t* keep) {
-    KLAUNCH(decode_velodyne_keep_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d, n, step, ox, oy, oz, n_scans, keep);
+void launch_decode_velodyne_keep(hipStream_t s, const uint8_t* d, int n, int step, int ox, int oy, int oz, float q_lo, float q_hi, int32_t* keep) {
+    KLAUNCH(decode_velodyne_keep_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d, n, step, ox, oy, oz, q_lo, q_hi, keep);
 }
 void launch_decode_velodyne_emit(hipStream_t s, const uint8_t* d, int n, int step, int ox, int oy, int oz, int oi, const int32_t* keep, const int32_t* pos, float* out,
                                  int32_t* n_out) {

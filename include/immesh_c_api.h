@@ -255,7 +255,9 @@ int immesh_decode_livox(immesh_ctx* ctx, const uint8_t* wire_points, int32_t n, 
                         float* out_xyzit, int32_t* n_out);
 /* void Preprocess::velodyne_handler(const sensor_msgs::PointCloud2::ConstPtr&)   src/preprocess.cpp:497-526.  data: msg->data (n points of
  * point_step bytes); off_*: byte offsets of the float32 fields x, y, z, intensity (msg->fields).  Keeps the points whose elevation
- * atan(z / sqrt(x^2+y^2)) lies in [-24.33, 2] degrees and whose HDL-64 scan id is in [0, 50]; curvature is 0 (the handler does not set it). */
+ * atan(z / sqrt(x^2+y^2)) lies in [-24.33, 2] degrees and whose HDL-64 scan id is in [0, 50]; curvature is 0 (the handler does not set it).
+ * Points with a NaN elevation (the origin, a NaN coordinate) are dropped.  IMMESH_E_INVAL: point_step outside 16..64, a field outside the
+ * point, a negative offset, n_scans < 1. */
 int immesh_decode_velodyne(immesh_ctx* ctx, const uint8_t* data, int32_t n, int32_t point_step, int32_t off_x, int32_t off_y, int32_t off_z,
                            int32_t off_intensity, int32_t n_scans, float* out_xyzit, int32_t* n_out);
 const float* immesh_decode_result(immesh_ctx* ctx);

@@ -177,6 +177,9 @@ inline int decode_velodyne(const uint8_t* data, int n, int step, int ox, int oy,
         float x, y, z, inten;
         std::memcpy(&x, p + ox, 4); std::memcpy(&y, p + oy, 4); std::memcpy(&z, p + oz, 4); std::memcpy(&inten, p + oi, 4);
         const float angle = (float)((double)(std::atan(z / std::sqrt(x * x + y * y)) * 180) / M_PI);   // float atan / sqrt overloads
+        // a NaN angle ((0,0,0) is 0/0, or any NaN coordinate) is dropped: the reference converts it with int(), which on x86-64 (cvttsd2si)
+        // gives INT_MIN, so scan_id < 0.  Stated here instead of relying on that undefined conversion.
+        if (std::isnan(angle)) continue;
         int scan_id;
         if (angle >= -8.83) scan_id = int((2 - angle) * 3.0 + 0.5);
         else scan_id = n_scans / 2 + int((-8.83 - angle) * 2.0 + 0.5);

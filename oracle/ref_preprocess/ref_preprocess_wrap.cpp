@@ -18,7 +18,7 @@
 typedef unsigned int uint;
 typedef pcl::PointXYZINormal PointType;                 /* include/common_lib.h:58 */
 typedef pcl::PointCloud< PointType > PointCloudXYZI;   /* include/common_lib.h:59; the stub's PointCloud has clear / reserve / resize / push_back / operator[] / size */
-using std::vector;
+using namespace std;   /* src/preprocess.h:48, include/common_lib.h:23: the float atan / sqrt overloads, as velodyne_handler's angle has them in the project */
 struct orgtype { double range = 0, dista = 0; };      /* src/preprocess.h:84-101: the two members the (disabled) feature branch writes */
 namespace livox_ros_driver {
 struct CustomPoint { uint32_t offset_time; float x, y, z; uint8_t reflectivity, tag, line; };

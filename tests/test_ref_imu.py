@@ -12,7 +12,7 @@ import pytest
 
 from immesh_amd import capi, synth
 from conftest import make_oracle, ROOT
-from test_undistort import _package, _state, _cfg_identity
+from test_undistort import _package, _state, _cfg_identity, _edge_packages, _edge_ctx, _bits
 
 VP = C.c_void_p
 
@@ -81,6 +81,31 @@ def test_undistort_pcl_of_the_reference_equals_the_oracle(oracle_lib, ref_imu, c
         assert lut_r == lut_o
         assert ic_r.last_lidar_end_time == ic_o.last_lidar_end_time and ic_r.last_imu.t == ic_o.last_imu.t
         np.testing.assert_allclose(list(ic_r.acc_s_last) + list(ic_r.angvel_last), list(ic_o.acc_s_last) + list(ic_o.angvel_last), rtol=0, atol=1e-12)
+
+
+def test_undistort_pcl_of_the_reference_equals_the_oracle_at_the_edges(oracle_lib, ref_imu):
+    """Stamps on the IMU samples (the strict > rule), runs of equal stamps, +0.0 and -0.0, stamps outside the IMU span, the earliest point in
+    several intervals, one point, no IMU sample, 62 samples, a last point that is not the latest.  The reference's std::sort is unstable: within
+    a group of equal stamps its points are compared as a set (the intensity column is the arrival index); the groups themselves, in order."""
+    cfg = capi.avia_config(cap_root_voxels=1 << 10, cap_scan_points=200000, cap_vertices=1 << 12, cap_triangles=1 << 14)
+    o = make_oracle(oracle_lib, cfg)
+    for name, pts, imu in _edge_packages():
+        ic_o, st0 = _edge_ctx(cfg)
+        ic_r = _copy_ic(ic_o)
+        out_o, st_o, lut_o = o.undistort(pts, imu, 0.0, 0.0, ic_o, st0)
+        out_r, st_r, lut_r = _ref_undistort(ref_imu, pts, imu, 0.0, 0.0, ic_r, st0)
+        t = pts[np.argsort(pts[:, 4], kind="stable"), 4]
+        np.testing.assert_array_equal(out_o[:, 3], pts[np.argsort(pts[:, 4], kind="stable"), 3])   # the oracle: stable, -0.0 == +0.0
+        group = np.concatenate([[0], np.cumsum(t[1:] != t[:-1])])
+        assert t[0] <= 0 or len(t) == 1 or group[1] > 0, name                      # (a tie at a compensated minimum would make "earliest" ambiguous)
+        r = out_r[np.lexsort((out_r[:, 3], group))]                         # the reference's rows in group order, by arrival inside a group
+        np.testing.assert_array_equal(r[:, 3], out_o[:, 3], err_msg=name)
+        d = np.abs(r[:, :3].astype(np.float64) - out_o[:, :3])
+        assert np.all(d <= np.spacing(np.abs(out_o[:, :3]))), name        # one float spacing
+        assert np.mean(_bits(r[:, :3]) == _bits(out_o[:, :3])) > 0.999, name
+        np.testing.assert_allclose(st_r[:24], st_o[:24], rtol=0, atol=1e-12, err_msg=name)
+        np.testing.assert_allclose(st_r[24:], st_o[24:], rtol=1e-12, atol=1e-18, err_msg=name)
+        assert lut_r == lut_o and ic_r.last_lidar_end_time == ic_o.last_lidar_end_time, name
 
 
 def test_forward_without_imu_of_the_reference_equals_the_product_and_the_harness(ref_imu):

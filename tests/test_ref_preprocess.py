@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import make_oracle, ROOT
-from test_decode import _cfg, _livox_msg, _velo_msg
+from test_decode import _cfg, _livox_msg, _velo_msg, _livox_edge_cases, _velo_gate_xyzi, _velo_pack, _bits, VELO_LAYOUTS, VELO_N_SCANS
 
 VP = C.c_void_p
 
@@ -53,3 +53,32 @@ def test_velodyne_handler_of_the_reference_equals_the_oracle(oracle_lib, ref_pp)
             nr = ref_pp.rp_velodyne(d.ctypes.data_as(VP), n, 32, 0, 4, 8, 16, n_scans, out.ctypes.data_as(VP), n)
             assert nr == no and 0 < no < n
             np.testing.assert_array_equal(out[:nr, :4], oo[:no, :4])   # (the handler leaves curvature unset: PointType's 0)
+
+
+def test_avia_handler_of_the_reference_equals_the_oracle_at_the_gates(oracle_lib, ref_pp):
+    """blind^2 and one float either side, reflectivity 4 / 5, line n_scans - 1 / n_scans / 255, NaN coordinates, stamps above 2^24, a filter
+    above the number of valid points, n = 1, no valid line."""
+    o = make_oracle(oracle_lib, _cfg())
+    for m, n_scans, filt, blind in _livox_edge_cases():
+        w = np.ascontiguousarray(m.view(np.uint8).reshape(-1, 19))
+        oo, no = o.decode_livox(w, n_scans, filt, blind)
+        out = np.zeros((len(m), 5), np.float32)
+        nr = ref_pp.rp_avia(w.ctypes.data_as(VP), len(m), n_scans, filt, blind, out.ctypes.data_as(VP), len(m))
+        assert nr == no, (len(m), filt, blind)
+        np.testing.assert_array_equal(_bits(out[:nr]), _bits(oo[:no]))
+
+
+def test_velodyne_handler_of_the_reference_equals_the_oracle_at_the_gates(oracle_lib, ref_pp):
+    """Every float within 4096 spacings of each elevation gate, the origin, +-90 deg, NaN / inf in each coordinate, subnormals: the same points
+    kept bit for bit (the reference drops the NaN elevations through int(NaN) == INT_MIN, the oracle by an explicit test), for every layout."""
+    o = make_oracle(oracle_lib, _cfg())
+    xyzi = _velo_gate_xyzi()
+    n = len(xyzi)
+    for step, offs in VELO_LAYOUTS:
+        d = np.ascontiguousarray(_velo_pack(xyzi, step, offs))
+        for n_scans in VELO_N_SCANS:
+            oo, no = o.decode_velodyne(d, step, offs, n_scans)
+            out = np.zeros((n, 5), np.float32)
+            nr = ref_pp.rp_velodyne(d.ctypes.data_as(VP), n, step, *offs, n_scans, out.ctypes.data_as(VP), n)
+            assert nr == no and 0 < no < n, (step, n_scans)
+            np.testing.assert_array_equal(_bits(out[:nr, :4]), _bits(oo[:no, :4]))
