@@ -119,6 +119,36 @@ class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 56), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
 
+class Camera(C.Structure):
+    """immesh_camera (include/immesh_render.h): the depth view of LiDAR point reinforcement"""
+    _fields_ = [("rot", C.c_double * 9), ("pos", C.c_double * 3), ("width", C.c_int32), ("height", C.c_int32), ("focus", C.c_double),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("downsample_res", C.c_double)]
+
+
+def default_depth_camera(lib, **over):
+    """immesh_default_depth_camera (640 x 480, focus 400, 0.05 / 200, cell 0.01, identity pose) with fields overridden by keyword"""
+    cam = Camera()
+    lib.immesh_default_depth_camera.argtypes = [C.POINTER(Camera)]; lib.immesh_default_depth_camera.restype = None
+    lib.immesh_default_depth_camera(C.byref(cam))
+    for k, v in over.items():
+        if k in ("rot", "pos"):
+            getattr(cam, k)[:] = [float(x) for x in np.asarray(v, float).reshape(-1)]
+        else:
+            setattr(cam, k, v)
+    return cam
+
+
+def camera_from_state(lib, state, cam=None):
+    """immesh_camera_from_state: the pose of `cam` (default: the default depth camera) from a state vector (make_state layout)"""
+    cam = default_depth_camera(lib) if cam is None else cam
+    st = np.ascontiguousarray(state, dtype=np.float64)
+    f = lib.immesh_camera_from_state; f.argtypes = [C.c_void_p, C.POINTER(Camera)]; f.restype = C.c_int
+    rc = f(st.ctypes.data_as(C.c_void_p), C.byref(cam))
+    if rc != 0:
+        raise RuntimeError(f"immesh_camera_from_state failed rc={rc}")
+    return cam
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in COUNTER_FIELDS]
 
@@ -251,6 +281,10 @@ class HotPath:
         self.ctx = C.c_void_p(self.ctx)
 
     def close(self):
+        if getattr(self, "_renderer", None):                 # the renderer goes before its context
+            g = self.lib.immesh_renderer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
+            g(self._renderer)
+            self._renderer = None
         if self.ctx:
             d = self._f("destroy"); d.argtypes = [C.c_void_p]; d.restype = None
             d(self.ctx)
@@ -389,6 +423,61 @@ class HotPath:
     def save_ply(self, path, smooth_factor=1.0, knn=20):
         f = self._f("save_ply"); f.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_int32]; f.restype = C.c_int
         self._check(f(self.ctx, path.encode(), smooth_factor, knn), "save_ply")
+
+    # -- mesh depth images + LiDAR point reinforcement (include/immesh_render.h) --------------------------------------------------------------
+    def renderer(self):
+        """the context's renderer (created at first use, destroyed by close())"""
+        if getattr(self, "_renderer", None) is None:
+            f = self.lib.immesh_renderer_create; f.argtypes = [C.c_void_p]; f.restype = C.c_void_p
+            r = f(self.ctx)
+            if not r:
+                self._check(-1, "renderer_create")
+            self._renderer = C.c_void_p(r)
+        return self._renderer
+
+    def camera_from_state(self, state, cam=None):
+        return camera_from_state(self.lib, state, cam)
+
+    def default_depth_camera(self, **over):
+        return default_depth_camera(self.lib, **over)
+
+    def render_triangles(self, cam, vtx_xyz, faces, want_depth=True, want_face=True):
+        """immesh_render_triangles on a host triangle soup -> (depth (h, w) float32 or None, face (h, w) int32 or None)"""
+        f = self.lib.immesh_render_triangles
+        f.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        vtx = np.ascontiguousarray(vtx_xyz, dtype=np.float32).reshape(-1, 3)
+        fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        shape = (max(cam.height, 0), max(cam.width, 0))               # (a bad size is the library's to reject)
+        depth = np.empty(shape, np.float32) if want_depth else None
+        face = np.empty(shape, np.int32) if want_face else None
+        self._check(f(self.renderer(), C.byref(cam), _ptr(vtx), len(vtx), _ptr(fc), len(fc), _ptr(depth), _ptr(face)), "render_triangles")
+        return depth, face
+
+    def render_mesh(self, cam, smooth_factor=1.0, knn=20, want_depth=True, want_face=True):
+        """immesh_render_mesh: the live mesh as mesh_export(smooth_factor, knn) exports it -> (depth, face)"""
+        f = self.lib.immesh_render_mesh
+        f.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_double, C.c_int32, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        shape = (max(cam.height, 0), max(cam.width, 0))
+        depth = np.empty(shape, np.float32) if want_depth else None
+        face = np.empty(shape, np.int32) if want_face else None
+        self._check(f(self.renderer(), C.byref(cam), smooth_factor, knn, _ptr(depth), _ptr(face)), "render_mesh")
+        return depth, face
+
+    def render_points(self):
+        """reinforced points of the last render, pixel order -> (n, 3) float32"""
+        f = self.lib.immesh_render_points; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.renderer(), None, 0, C.byref(n)), "render_points")
+        out = np.zeros((n.value, 3), np.float32)
+        self._check(f(self.renderer(), _ptr(out), n.value, C.byref(n)), "render_points")
+        return out
+
+    def render_timing(self):
+        """device milliseconds of the last render: (rasterize, reinforce)"""
+        f = self.lib.immesh_renderer_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.renderer(), ms), "renderer_last_timing")
+        return float(ms[0]), float(ms[1])
 
     def process_scan_strided(self, down_bytes, n_ds, down_stride, raw_bytes, n_raw, raw_stride, raw_int_off, state_prior, state, frame_idx=0, do_mesh=True):
         """immesh_process_scan_strided: down_bytes / raw_bytes = numpy arrays (any dtype) or device pointers holding the pcl-shaped clouds"""

@@ -1,0 +1,259 @@
+// Host side of the mesh depth rasterizer (include/immesh_render.h): argument checks, grow-only buffers, the launch sequence on the renderer's stream.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "../host_ctx.hpp"
+#include "render.hpp"
+
+struct RdBuf {   // grow-only device buffer
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+struct immesh_renderer {
+    immesh_ctx* ctx = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int64_t* h_small = nullptr;   // pinned: [0] pairs of the render, [1] reinforced points
+    RdBuf vtx, faces, rec, cnt, foff, temp, tiles, bins, depth, face, pts, cells, keep, koff, slot, tab, out, small;
+    int64_t n_points = 0;
+    float ms[2] = {0.0f, 0.0f};
+};
+
+namespace {
+
+int rd_grow(immesh_renderer* r, RdBuf& b, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (b.bytes >= bytes) return 0;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.bytes = 0;
+    const size_t want = bytes + bytes / 4;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        r->ctx->err = "render: hipMalloc(" + std::to_string(want) + " B) failed";
+        return IMMESH_E_NOMEM;
+    }
+    b.bytes = want;
+    return 0;
+}
+
+int rd_check_camera(immesh_renderer* r, const immesh_camera* cam) {
+    if (!cam) { r->ctx->err = "render: camera is NULL"; return IMMESH_E_INVAL; }
+    if (cam->width <= 0 || cam->height <= 0 || cam->width > 8192 || cam->height > 8192) {
+        r->ctx->err = "render: width and height must be in 1..8192 (got " + std::to_string(cam->width) + " x " + std::to_string(cam->height) + ")";
+        return IMMESH_E_INVAL;
+    }
+    if (!(cam->focus > 0.0) || !std::isfinite(cam->focus)) { r->ctx->err = "render: focus must be finite and > 0"; return IMMESH_E_INVAL; }
+    if (!(cam->z_near > 0.0) || !(cam->z_near < cam->z_far) || !std::isfinite(cam->z_far)) {
+        r->ctx->err = "render: need 0 < z_near < z_far, both finite";
+        return IMMESH_E_INVAL;
+    }
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(cam->rot[i])) { r->ctx->err = "render: camera rotation is not finite"; return IMMESH_E_INVAL; }
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(cam->pos[i])) { r->ctx->err = "render: camera position is not finite"; return IMMESH_E_INVAL; }
+    if (std::isnan(cam->downsample_res)) { r->ctx->err = "render: downsample_res is NaN"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+// rasterize n_faces faces of device arrays (vtx n_vtx x 3 floats, faces n_faces x 3 ints), reinforce, copy the requested outputs to the host
+int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, int64_t n_vtx, const int32_t* d_faces, int64_t n_faces, float* depth_out,
+              int32_t* face_out) {
+    immesh_ctx* c = r->ctx;
+    hipStream_t s = r->s;
+    r->n_points = 0;
+    RdCam rc;
+    std::memcpy(rc.rot, cam->rot, sizeof(rc.rot));
+    std::memcpy(rc.pos, cam->pos, sizeof(rc.pos));
+    rc.f = cam->focus; rc.z_near = cam->z_near; rc.z_far = cam->z_far;
+    rc.w = cam->width; rc.h = cam->height; rc.cx = cam->width / 2; rc.cy = cam->height / 2;
+    rc.tiles_x = (rc.w + RD_TILE - 1) / RD_TILE; rc.tiles_y = (rc.h + RD_TILE - 1) / RD_TILE;
+    const int n_tiles = rc.tiles_x * rc.tiles_y;
+    const int64_t n_pix = (int64_t)rc.w * rc.h;
+    const float res = (float)cam->downsample_res;
+    int rc_ = 0;
+    if ((rc_ = rd_grow(r, r->rec, (size_t)n_faces * sizeof(RdFace)))) return rc_;
+    if ((rc_ = rd_grow(r, r->cnt, (size_t)n_faces * 8))) return rc_;
+    if ((rc_ = rd_grow(r, r->foff, (size_t)(n_faces + 1) * 8))) return rc_;
+    if ((rc_ = rd_grow(r, r->temp, rd_scan_temp_bytes(n_faces, n_tiles, n_pix) + 256))) return rc_;
+    if ((rc_ = rd_grow(r, r->tiles, (size_t)n_tiles * 12))) return rc_;
+    if ((rc_ = rd_grow(r, r->depth, (size_t)n_pix * 4))) return rc_;
+    if ((rc_ = rd_grow(r, r->face, (size_t)n_pix * 4))) return rc_;
+    if ((rc_ = rd_grow(r, r->pts, (size_t)n_pix * 12))) return rc_;
+    if ((rc_ = rd_grow(r, r->keep, (size_t)n_pix * 4))) return rc_;
+    if ((rc_ = rd_grow(r, r->koff, (size_t)n_pix * 4))) return rc_;
+    if ((rc_ = rd_grow(r, r->out, (size_t)n_pix * 12))) return rc_;
+    if ((rc_ = rd_grow(r, r->small, 16))) return rc_;
+    uint32_t mask = 0;
+    if (res > 0.0f) {
+        uint64_t cap = 1024;
+        while (cap < 2 * (uint64_t)n_pix) cap <<= 1;
+        mask = (uint32_t)(cap - 1);
+        if ((rc_ = rd_grow(r, r->cells, (size_t)n_pix * 12))) return rc_;
+        if ((rc_ = rd_grow(r, r->slot, (size_t)n_pix * 4))) return rc_;
+        if ((rc_ = rd_grow(r, r->tab, (size_t)cap * 8))) return rc_;
+    }
+    RdFace* rec = (RdFace*)r->rec.p;
+    int64_t* cnt = (int64_t*)r->cnt.p;
+    int64_t* foff = (int64_t*)r->foff.p;
+    int32_t* tile_cnt = (int32_t*)r->tiles.p;
+    int32_t* tile_off = tile_cnt + n_tiles;
+    int32_t* tile_fill = tile_off + n_tiles;
+    float* depth = (float*)r->depth.p;
+    int32_t* face = (int32_t*)r->face.p;
+
+    // ---- rasterize
+    HIPCHK(c, hipEventRecord(r->ev[0], s));
+    rd_launch_setup(s, rc, d_vtx, n_vtx, d_faces, n_faces, rec, cnt);
+    rd_scan_pairs(s, r->temp.p, r->temp.bytes, cnt, foff, n_faces);
+    HIPCHK(c, hipMemcpyAsync(r->h_small, foff + n_faces, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const int64_t n_pairs = r->h_small[0];
+    if (n_pairs > (int64_t)INT_MAX) {
+        c->err = "render: " + std::to_string(n_pairs) + " (face, tile) pairs in one render, more than 2^31 - 1";
+        return IMMESH_E_CAPACITY;
+    }
+    if ((rc_ = rd_grow(r, r->bins, (size_t)n_pairs * 4))) return rc_;
+    HIPCHK(c, hipMemsetAsync(tile_cnt, 0, (size_t)n_tiles * 12, s));
+    rd_launch_bin(s, rc, rec, foff, n_faces, n_pairs, 0, tile_cnt, nullptr, nullptr, nullptr);
+    rd_scan_i32(s, r->temp.p, r->temp.bytes, tile_cnt, tile_off, n_tiles);
+    rd_launch_bin(s, rc, rec, foff, n_faces, n_pairs, 1, tile_cnt, tile_off, tile_fill, (int32_t*)r->bins.p);
+    rd_launch_resolve(s, rc, rec, tile_cnt, tile_off, (const int32_t*)r->bins.p, depth, face);
+    HIPCHK(c, hipEventRecord(r->ev[1], s));
+
+    // ---- reinforce
+    int32_t* keep = (int32_t*)r->keep.p;
+    rd_launch_unproject(s, rc, res, depth, (float*)r->pts.p, (float*)r->cells.p, keep);
+    if (res > 0.0f) {
+        int32_t* tab_rep = (int32_t*)r->tab.p;
+        uint32_t* tab_min = (uint32_t*)(tab_rep + (size_t)mask + 1);
+        HIPCHK(c, hipMemsetAsync(tab_rep, 0xFF, ((size_t)mask + 1) * 8, s));   // rep -1, min 0xFFFFFFFF
+        rd_launch_hash_insert(s, n_pix, depth, (const float*)r->cells.p, tab_rep, tab_min, mask, (uint32_t*)r->slot.p);
+        rd_launch_hash_keep(s, n_pix, depth, tab_min, (const uint32_t*)r->slot.p, keep);
+    }
+    rd_scan_i32(s, r->temp.p, r->temp.bytes, keep, (int32_t*)r->koff.p, n_pix);
+    rd_launch_compact(s, n_pix, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
+    HIPCHK(c, hipEventRecord(r->ev[2], s));
+    HIPCHK(c, hipMemcpyAsync(r->h_small + 1, r->small.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    r->n_points = r->h_small[1];
+    (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);
+    (void)hipEventElapsedTime(&r->ms[1], r->ev[1], r->ev[2]);
+    if (depth_out) HIPCHK(c, hipMemcpy(depth_out, depth, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
+    if (face_out) HIPCHK(c, hipMemcpy(face_out, face, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void immesh_default_depth_camera(immesh_camera* cam) {
+    if (!cam) return;
+    std::memset(cam, 0, sizeof(*cam));
+    cam->rot[0] = cam->rot[4] = cam->rot[8] = 1.0;
+    cam->width = 640; cam->height = 480;
+    cam->focus = 400.0;
+    cam->z_near = 0.05; cam->z_far = 200.0;
+    cam->downsample_res = 0.01;
+}
+
+int immesh_camera_from_state(const double* state, immesh_camera* cam) {
+    if (!state || !cam) return IMMESH_E_INVAL;
+    static const double M[9] = {0, 0, -1, -1, 0, 0, 0, 1, 0};   // lidar_frame_to_camera_frame, ImMesh_node.cpp:174
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) cam->rot[3 * i + j] = (state[3 * i] * M[j] + state[3 * i + 1] * M[3 + j]) + state[3 * i + 2] * M[6 + j];
+    for (int i = 0; i < 3; i++) cam->pos[i] = state[9 + i];
+    return 0;
+}
+
+immesh_renderer* immesh_renderer_create(immesh_ctx* ctx) {
+    if (!ctx) return nullptr;
+    (void)hipSetDevice(ctx->cfg.device);
+    immesh_renderer* r = new immesh_renderer();
+    r->ctx = ctx;
+    bool ok = hipStreamCreateWithFlags(&r->s, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 3 && ok; i++) ok = hipEventCreate(&r->ev[i]) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&r->h_small, 16) == hipSuccess;
+    if (!ok) {
+        ctx->err = "immesh_renderer_create: stream / event / pinned allocation failed";
+        immesh_renderer_destroy(r);
+        return nullptr;
+    }
+    return r;
+}
+
+void immesh_renderer_destroy(immesh_renderer* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->ctx->cfg.device);
+    if (r->s) (void)hipStreamSynchronize(r->s);
+    for (RdBuf* b : {&r->vtx, &r->faces, &r->rec, &r->cnt, &r->foff, &r->temp, &r->tiles, &r->bins, &r->depth, &r->face, &r->pts, &r->cells, &r->keep,
+                     &r->koff, &r->slot, &r->tab, &r->out, &r->small})
+        if (b->p) (void)hipFree(b->p);
+    for (hipEvent_t e : r->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (r->h_small) (void)hipHostFree(r->h_small);
+    if (r->s) (void)hipStreamDestroy(r->s);
+    delete r;
+}
+
+int immesh_render_triangles(immesh_renderer* r, const immesh_camera* cam, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces,
+                            float* depth_out, int32_t* face_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    int rc = rd_check_camera(r, cam);
+    if (rc) return rc;
+    if (n_vtx < 0 || n_faces < 0 || n_faces >= (int64_t)INT_MAX || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
+        c->err = "render_triangles: bad vertex / face arrays";
+        return IMMESH_E_INVAL;
+    }
+    for (int64_t i = 0; i < 3 * n_faces; i++)
+        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
+            c->err = "render_triangles: face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
+                     std::to_string(n_vtx) + ")";
+            return IMMESH_E_INVAL;
+        }
+    (void)hipSetDevice(c->cfg.device);
+    if ((rc = rd_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
+    if ((rc = rd_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
+    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
+    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
+    return rd_render(r, cam, (const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p, n_faces, depth_out, face_out);
+}
+
+int immesh_render_mesh(immesh_renderer* r, const immesh_camera* cam, double smooth_factor, int32_t knn, float* depth_out, int32_t* face_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    int rc = rd_check_camera(r, cam);
+    if (rc) return rc;
+    int64_t nv = 0, nf = 0;
+    if ((rc = immesh_mesh_export(c, smooth_factor, knn, &nv, &nf))) return rc;   // synchronises the ctx stream: the arrays are complete
+    if (nf >= (int64_t)INT_MAX) { c->err = "render_mesh: more than 2^31 - 2 faces"; return IMMESH_E_CAPACITY; }
+    const MeshHost& h = c->mesh_host;
+    (void)hipSetDevice(c->cfg.device);
+    return rd_render(r, cam, (const float*)h.exp_vtx, nv, h.exp_faces, nf, depth_out, face_out);
+}
+
+int immesh_render_points(immesh_renderer* r, float* xyz_out, int64_t cap, int64_t* n_out) {
+    if (!r) return IMMESH_E_INVAL;
+    if (n_out) *n_out = r->n_points;
+    if (!xyz_out || r->n_points == 0) return 0;
+    if (cap < r->n_points) {
+        r->ctx->err = "render_points: cap " + std::to_string(cap) + " < " + std::to_string(r->n_points) + " points";
+        return IMMESH_E_CAPACITY;
+    }
+    (void)hipSetDevice(r->ctx->cfg.device);
+    HIPCHK(r->ctx, hipMemcpy(xyz_out, r->out.p, (size_t)r->n_points * 12, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int immesh_renderer_last_timing(immesh_renderer* r, float ms[2]) {
+    if (!r || !ms) return IMMESH_E_INVAL;
+    ms[0] = r->ms[0]; ms[1] = r->ms[1];
+    return 0;
+}
+
+}  // extern "C"
