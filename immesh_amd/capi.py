@@ -149,6 +149,15 @@ def camera_from_state(lib, state, cam=None):
     return cam
 
 
+class RegionInfo(C.Structure):
+    """immesh_region_info (include/immesh_regions.h): one region bucket of the renderer"""
+    _fields_ = [("key", C.c_int32 * 3), ("index", C.c_int32), ("n_triangles", C.c_int32), ("dirty", C.c_int32), ("first", C.c_int64)]
+
+
+REGION_DTYPE = np.dtype([("key", "<i4", 3), ("index", "<i4"), ("n_triangles", "<i4"), ("dirty", "<i4"), ("first", "<i8")])
+assert REGION_DTYPE.itemsize == C.sizeof(RegionInfo) == 32
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in COUNTER_FIELDS]
 
@@ -423,6 +432,56 @@ class HotPath:
     def save_ply(self, path, smooth_factor=1.0, knn=20):
         f = self._f("save_ply"); f.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_int32]; f.restype = C.c_int
         self._check(f(self.ctx, path.encode(), smooth_factor, knn), "save_ply")
+
+    # -- the renderer's region buckets on the device (include/immesh_regions.h) -------------------------------------------------------------
+    def _check_regions(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"immesh_{what} failed rc={rc}: {self.mesh_regions_error()}")
+
+    def mesh_regions_error(self):
+        f = self.lib.immesh_mesh_regions_error; f.argtypes = [C.c_void_p]; f.restype = C.c_char_p
+        return f(self.ctx).decode()
+
+    def mesh_regions_enable(self, on=True):
+        """switch the device's region table on -- before the first mesh job of the context"""
+        f = self.lib.immesh_mesh_regions_enable; f.argtypes = [C.c_void_p, C.c_int32]; f.restype = C.c_int
+        self._check_regions(f(self.ctx, 1 if on else 0), "mesh_regions_enable")
+
+    def mesh_regions(self):
+        """the whole region table in index (creation) order -> structured array (REGION_DTYPE); flags untouched"""
+        f = self.lib.immesh_mesh_regions; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]; f.restype = C.c_int
+        n = C.c_int32(0)
+        self._check_regions(f(self.ctx, None, 0, C.byref(n)), "mesh_regions")
+        out = np.zeros(n.value, REGION_DTYPE)
+        if n.value:
+            self._check_regions(f(self.ctx, _ptr(out), n.value, C.byref(n)), "mesh_regions")
+        return out[:n.value]
+
+    def mesh_regions_fetch(self, n_regions, n_triangles):
+        """results of the last mesh_regions_sync -> {"regions" (REGION_DTYPE), "tri" (n, 3) int32, "flip" (n) uint8, "xyz" (n, 3, 3) float32}"""
+        f = self.lib.immesh_mesh_regions_fetch; f.argtypes = [C.c_void_p] * 5; f.restype = C.c_int
+        r = {"regions": np.zeros(n_regions, REGION_DTYPE), "tri": np.zeros((n_triangles, 3), np.int32), "flip": np.zeros(n_triangles, np.uint8),
+             "xyz": np.zeros((n_triangles, 3, 3), np.float32)}
+        self._check_regions(f(self.ctx, _ptr(r["regions"]), _ptr(r["tri"]), _ptr(r["flip"]), _ptr(r["xyz"])), "mesh_regions_fetch")
+        return r
+
+    def mesh_regions_sync(self, smooth_factor=1.0, knn=20, maximum_smooth_dis=0.0, force_all=False, fetch=True):
+        """synchronize_triangle_list_for_disp on the device: the regions changed since the last sync (all with force_all), each with its live triangles
+        (sorted triplets, flip bytes, nine display floats); region k's triangles are rows regions["first"][k] : + regions["n_triangles"][k]"""
+        f = self.lib.immesh_mesh_regions_sync
+        f.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]; f.restype = C.c_int
+        nr, nt = C.c_int32(0), C.c_int64(0)
+        self._check_regions(f(self.ctx, smooth_factor, knn, maximum_smooth_dis, 1 if force_all else 0, C.byref(nr), C.byref(nt)), "mesh_regions_sync")
+        return self.mesh_regions_fetch(nr.value, nt.value) if fetch else (nr.value, nt.value)
+
+    def region_keys(self, vtx_xyz, tri):
+        """immesh_region_keys: the key rule evaluated on the device for caller-supplied triangles -> (n, 3) int32"""
+        f = self.lib.immesh_region_keys; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        vtx = np.ascontiguousarray(vtx_xyz, dtype=np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((len(t), 3), np.int32)
+        self._check_regions(f(self.ctx, _ptr(vtx), len(vtx), _ptr(t), len(t), _ptr(out)), "region_keys")
+        return out
 
     # -- mesh depth images + LiDAR point reinforcement (include/immesh_render.h) --------------------------------------------------------------
     def renderer(self):

@@ -2,6 +2,7 @@
 // as a sequence of launches on the context stream.  No per-point / per-voxel / per-triangle work happens on the host: it only
 // sizes launches from a handful of device counters and moves the result lists on immesh_mesh_fetch.
 #include "host_ctx.hpp"
+#include "regions/regions.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -192,6 +193,7 @@ int mesh_alloc(immesh_ctx* c) {
     }
     for (int k = 0; k < MESH_NPAR; k++) std::memset(&h.res[k].sizes, 0, sizeof(immesh_mesh_sizes_t));
     h.stop = false;
+    if ((rc = regions_create(c))) return rc;   // (host record only: the table is allocated by immesh_mesh_regions_enable)
     h.worker = std::thread(mesh_worker_main, c);
     h.ready = true;
     return 0;
@@ -232,6 +234,7 @@ void mesh_free(immesh_ctx* c) {
     if (h.stream_fetch) { (void)hipStreamSynchronize(h.stream_fetch); (void)hipStreamDestroy(h.stream_fetch); h.stream_fetch = nullptr; }
     if (h.h_fetch) { (void)hipHostFree(h.h_fetch); h.h_fetch = nullptr; h.h_fetch_bytes = 0; }
     h.stream_q = nullptr;
+    regions_free(c);
     if (h.q_host) { (void)hipHostFree(h.q_host); h.q_host = nullptr; h.q_host_bytes = 0; }
     if (h.q_dev) { (void)hipFree(h.q_dev); h.q_dev = nullptr; h.q_dev_bytes = 0; }
     if (h.q_exp) { (void)hipFree(h.q_exp); h.q_exp = nullptr; h.q_exp_bytes = 0; }
@@ -263,8 +266,9 @@ static int mesh_overflow(immesh_ctx* c) {
     static const char* why[] = {"", "mesh-voxel hash full", "mesh-voxel pool exhausted (cap_vertices)", "candidate-cell table full", "vertex pool exhausted (cap_vertices)",
                                 "mesh voxel lookup failed", "dedupe grid hash full", "mesh voxel holds more than 128 vertices", "more active voxels than cap (131072 per scan)",
                                 "voxel neighbourhood above 1024 vertices", "triangle pool exhausted (cap_triangles)", "triangle hash full", "Delaunay cavity / triangle buffer overflow",
-                                "adjacency chunk pool exhausted", "per-scan result list above 4194304 entries"};
-    c->mesh_host.err = std::string("mesh map capacity: ") + why[(f > 0 && f < 15) ? f : 0];
+                                "adjacency chunk pool exhausted", "per-scan result list above 4194304 entries",
+                                "region table full (65536 regions) or a region key beyond 2^20"};
+    c->mesh_host.err = std::string("mesh map capacity: ") + why[(f > 0 && f < 16) ? f : 0];
     return IMMESH_E_CAPACITY;
 }
 
@@ -305,6 +309,7 @@ static int mesh_enqueue_b(immesh_ctx* c, const MeshDev& m, int par, hipStream_t 
     launch_mesh_finalize(s, m);                               // (+ the removals: Triangle_manager::remove_triangle_list)
     launch_mesh_sort_emit(s, m, 1, h.d_sort_recs, h.p_a);
     launch_mesh_commit_add(s, m, h.p_a);
+    regions_enqueue_mark(c, m, s, h.p_a);                     // (nothing unless immesh_mesh_regions_enable: the renderer's region buckets follow the commit)
     launch_mesh_publish(s, m, h.h_sc2_dev[par]);
     return 0;
 }

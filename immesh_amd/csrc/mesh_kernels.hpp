@@ -212,6 +212,7 @@ struct MeshHost {
     int64_t x_rounds = 0;                    // cumulative admission exchange rounds (>= 1 per scan; 2 when no dependency chain crosses a brick face twice)
     int fin_state[3] = {0, 0, 0};            // committed list lengths of the job being finished (sharded: sizes carry the reported parts)
     KProf prof;                              // kernels launched by the worker thread
+    struct RegionsHost* regions = nullptr;   // the renderer's region buckets (regions/regions.hpp, include/immesh_regions.h); off unless enabled
     std::string err;                         // worker-side error text (moved into the MeshResult of the failing job)
 };
 
