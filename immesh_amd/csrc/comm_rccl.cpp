@@ -164,9 +164,7 @@ int immesh_broadcast_scan(immesh_ctx* c, const float* pts, int32_t n, int32_t st
     float* buf = c->d_bcast[2 * par + (st == 4 ? 1 : 0)];
     const size_t bytes = (size_t)np * st * sizeof(float);
     if (am_root) {
-        hipPointerAttribute_t attr;
-        const bool dev_in = hipPointerGetAttributes(&attr, pts) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-        if (!dev_in) (void)hipGetLastError();
+        const bool dev_in = is_device_ptr(pts);
         if ((const void*)pts != (const void*)buf) HIPCHK(c, hipMemcpyAsync(buf, pts, bytes, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     }
     if (use_rccl) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #define IMD __device__ __forceinline__
+#define IMHD __host__ __device__ __forceinline__   /* also callable from the host layer (the sharding functions: one definition for kernels and host) */
 
 namespace imd {
 
@@ -98,10 +99,10 @@ IMD float loc_axis(const double q) {  // the float `loc_xyz` itself (needed by t
 #define IM_KEY_BIAS (1 << 20)
 #define IM_KEY_MASK ((1ull << 21) - 1)
 #define IM_KEY_EMPTY 0xFFFFFFFFFFFFFFFFull
-IMD uint64_t pack_key(int64_t x, int64_t y, int64_t z) {
+IMHD uint64_t pack_key(int64_t x, int64_t y, int64_t z) {
     return ((uint64_t)(x + IM_KEY_BIAS) & IM_KEY_MASK) | (((uint64_t)(y + IM_KEY_BIAS) & IM_KEY_MASK) << 21) | (((uint64_t)(z + IM_KEY_BIAS) & IM_KEY_MASK) << 42);
 }
-IMD uint64_t hash64(uint64_t k) {  // splitmix64 finaliser
+IMHD uint64_t hash64(uint64_t k) {  // splitmix64 finaliser
     k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
     k ^= k >> 27; k *= 0x94d049bb133111ebull;
     k ^= k >> 31;

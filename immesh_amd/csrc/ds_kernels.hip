@@ -552,7 +552,7 @@ __global__ void decode_livox_emit_kernel(const uint8_t* __restrict__ w, int n, c
     }
     if (i == n - 1) *n_out = pos[i] + keep_flag[i];
 }
-// the elevation gates as one interval of q = z / sqrtf(x*x + y*y) (velodyne_q_interval in c_api.cpp): the product, the correctly rounded
+// the elevation gates as one interval of q = z / sqrtf(x*x + y*y) (velodyne_q_interval in pre_host.cpp): the product, the correctly rounded
 // sqrtf and division (-ffp-contract=off) give the host's q bit for bit, so no device arctangent decides a point.  A NaN q fails both comparisons.
 __global__ void decode_velodyne_keep_kernel(const uint8_t* __restrict__ d, int n, int step, int ox, int oy, int oz, float q_lo, float q_hi,
                                             int32_t* __restrict__ keep) {

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <chrono>
+#include <thread>
 #include <string>
 #include <vector>
 #include <cstdio>
@@ -12,6 +14,7 @@
 #include "ikd_map.hpp"
 #include "ekf_host.hpp"
 #include "prof.hpp"
+#include "host_knobs.hpp"
 
 #define HIPCHK(ctx, expr)                                                                                   \
     do {                                                                                                    \
@@ -22,13 +25,19 @@
         }                                                                                                   \
     } while (0)
 
-struct DevBuf {  // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-};
+inline int64_t np2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return p; }   // next power of two
+
+// is this pointer device (or managed) memory?  A plain host pointer makes the query fail: the sticky error is cleared
+inline bool is_device_ptr(const void* p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
 
 struct immesh_ctx {
     immesh_config cfg;
+    Knobs knobs;                     // the environment switches, read once by immesh_create
+    int prio_least = 0;              // lowest stream priority of the device (0 under IMMESH_NO_PRIORITY): the mesher's streams
     std::string err;
     hipStream_t stream = nullptr;
     hipStream_t stream_pre = nullptr;    // the stages before the path (decode / undistort / down-sample): they do not touch the map, so they run beside the previous scan's map update
@@ -41,6 +50,7 @@ struct immesh_ctx {
     bool tail_deferred = false;      // ... and left the update's tail (free-list merge, counters to the host) to the next scan's residual_persistent_kernel
     float timing[4] = {0, 0, 0, 0};
     std::vector<void*> allocs;
+    std::vector<void*> pinned_blocks;   // pinned(): freed by immesh_destroy once the streams are drained
     size_t bytes_allocated = 0;
 
     // ---- registration map
@@ -60,7 +70,6 @@ struct immesh_ctx {
     double* d_partials = nullptr;    // residual block partials
     int rp_parity = 0;
     int rp_max_blocks = 127;         // grid cap of residual_persistent_kernel: half of the device's resident workgroups - 1 (occupancy query at create)
-    bool rp_force_abort = false;     // IMMESH_RP_FORCE_ABORT (tests): every resident-grid registration gives up in its first gather
     int64_t rp_fallbacks = 0;        // scans registered by the per-pass chain because the resident grid gave up
     // epilogue of the registration launch (map update preparation + full-scan transform): the "scan is in its world buffer / input clouds consumed" flag,
     // 64-bit at d_epi + 2 on the device (the mesher's first kernel polls it) and in pinned memory for the host; stored by the launch queued behind the
@@ -83,7 +92,7 @@ struct immesh_ctx {
     immesh_allreduce_fn allreduce = nullptr;   // sharded map: sums the per-rank partial normal equations
     void* allreduce_user = nullptr;
     unsigned long long* reg_dbg = nullptr;  // phase timers of residual_kernel (IMMESH_DEBUG)
-    unsigned long long res_ticket = 0;  // completion ticket of the last residual launch (polled in h_out48[47])
+    unsigned long long res_ticket = 0;  // completion ticket of the last residual launch (polled in h_out48[RES_TICKET])
     int8_t* d_match = nullptr;
     int32_t* d_mnode = nullptr;
     float* d_dis = nullptr;
@@ -143,16 +152,49 @@ struct immesh_ctx {
         *out = (T*)p;
         return 0;
     }
+    // a fixed-size block of pinned, device-mapped host memory, zero-filled; *dev (optional) = its device-side address
+    template <typename T>
+    int pinned(T** host, T** dev, size_t count) {
+        void* p = nullptr;
+        void* d = nullptr;
+        if (hipHostMalloc(&p, count * sizeof(T), hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); err = "hipHostMalloc(" + std::to_string(count * sizeof(T)) + " B)"; return IMMESH_E_NOMEM; }
+        pinned_blocks.push_back(p);
+        HIPCHK(this, hipHostGetDevicePointer(&d, p, 0));
+        std::memset(p, 0, count * sizeof(T));
+        *host = (T*)p;
+        if (dev) *dev = (T*)d;
+        return 0;
+    }
 };
+
+// Bounded wait for a word in pinned memory that a kernel stores: spin until `reached()` holds -- with `yield_after` set, with a pause per look and, after
+// that long, a yield per 1024 looks -- and hand over to stream `s` at `limit` (never spin unbounded; a faulted stream returns its error there).
+// *held = reached(), behind an acquire fence.
+constexpr std::chrono::microseconds WAIT_NO_YIELD = std::chrono::microseconds::max();
+template <typename Pred>
+inline int wait_pinned(immesh_ctx* c, hipStream_t s, Pred reached, std::chrono::milliseconds limit, std::chrono::microseconds yield_after, bool* held) {
+    const bool pause = yield_after != WAIT_NO_YIELD;
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (!reached()) {
+        if (pause) __builtin_ia32_pause();
+        if ((++spins & 0x3FF) != 0) continue;
+        const auto dt = std::chrono::steady_clock::now() - t0;
+        if (dt > limit) {
+            const hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess) { c->err = std::string(s == c->stream ? "hipStreamSynchronize(c->stream): " : "hipStreamSynchronize(c->stream_pre): ") + hipGetErrorString(e); return IMMESH_E_HIP; }
+            break;
+        }
+        if (pause && dt > yield_after) std::this_thread::yield();
+    }
+    *held = reached();
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return 0;
+}
 
 // resolve an input pointer that may be host or device memory; host data is staged into `staging` on the ctx stream
 inline int resolve_input(immesh_ctx* c, const void* p, size_t bytes, void* staging, const void** dev_out) {
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, p);
-    bool is_dev = false;
-    if (e == hipSuccess) is_dev = (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-    else (void)hipGetLastError();  // plain host pointer: clear the sticky error
-    if (is_dev) { *dev_out = p; return 0; }
+    if (is_device_ptr(p)) { *dev_out = p; return 0; }
     HIPCHK(c, hipMemcpyAsync(staging, p, bytes, hipMemcpyHostToDevice, c->stream));
     *dev_out = staging;
     return 0;

@@ -5,13 +5,12 @@
 #include <algorithm>
 #include <cmath>
 
-static int64_t ikd_np2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return p; }
 
 static int ikd_alloc(immesh_ctx* c) {
     IkdHost& h = c->ikd;
     if (h.ready) return 0;
     const int64_t cap_cells = c->cfg.cap_root_voxels > 0 ? c->cfg.cap_root_voxels : (1 << 20);
-    const int64_t slots = ikd_np2(cap_cells * 2);
+    const int64_t slots = np2(cap_cells * 2);
     int rc;
 #define A(ptr, n) if ((rc = c->dalloc(&(ptr), (size_t)(n)))) return rc
     A(h.m.keys, slots); A(h.m.count, slots); A(h.m.pts, slots * IKD_CELL_PTS); A(h.m.best, slots); A(h.m.stamp, slots);

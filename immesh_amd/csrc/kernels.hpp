@@ -27,8 +27,11 @@ struct PlaneRecDev {  // layout == immesh_plane_rec (include/immesh_c_api.h)
 
 #define REG_DBG_WORDS (64 + 16384 * 8 + 8 * 512 * 8)   /* IMMESH_DEBUG buffer (reg_kernels.hip DBG_*): counters + per-wavefront trace records */
 #define STATS_WORDS (16 + 64 * 16)   /* refit counters: [0] refits [1] refit points, then 64 shards of the fused replay kernel (one 128-byte line each) */
-#define RES_NV_HOST 48
-#define RES_NR_HOST 32
+#define RES_NV 48   /* the 48 sums of a residual pass (RES_* below) */
+#define RES_NR 32   /* reduced per block: 21 (upper triangle of HTH) + 6 HTz + 4 counters + 1 spare */
+// layout of the 48 sums (out48: pinned for REG_MODE_HOST, device memory for REG_MODE_SUMS), written by the residual kernels, read by the host and ekf_step_*
+enum { RES_HTH = 0, RES_HTZ = 36, RES_N_MATCH = 42, RES_SUM_DIS = 43, RES_PLANE_TESTS = 44, RES_EXTRA_PROBE = 45, RES_TICKET = 47 };
+static_assert(RES_TICKET == RES_NV - 1, "the ticket is the last of the 48 sums");
 
 // ---- device-resident iterated EKF (Voxel_mapping::lio_state_estimation, src/voxel_mapping.cpp:1585-1650) ---------------------
 // The state of the scan being registered stays on the device between the residual passes: the last block of a pass runs the 18-state
@@ -52,7 +55,19 @@ struct RegIterArgs {
     double st[24], prior[24];
     double mat[324];          // first pass: [0,36) P11^-1, [36,108) P21 P11^-1; later passes: the prior covariance
 };
-#define REG_OUT_DOUBLES 360   /* pinned result block: [0,348) posterior state, 348 passes run, 349 n_match (last pass), 350 sum|dis| (last pass), 351 plane tests, 352 extra probes, 353 n_match summed over the passes, 359 ticket */
+#define REG_OUT_DOUBLES 360   /* pinned result block of a registration (REG_OUT_* below) */
+enum {
+    REG_OUT_STATE = 0,          // [0,24) posterior state
+    REG_OUT_COV = 24,           // [24,348) posterior covariance (18 x 18)
+    REG_OUT_PASSES = 348,       // passes run (< 0: the resident grid gave up)
+    REG_OUT_N_MATCH = 349,      // n_match of the last pass
+    REG_OUT_SUM_DIS = 350,      // sum|dis| of the last pass
+    REG_OUT_PLANE_TESTS = 351,
+    REG_OUT_EXTRA_PROBE = 352,
+    REG_OUT_N_MATCH_SUM = 353,  // n_match summed over the passes
+    REG_OUT_TICKET = 359
+};
+static_assert(REG_OUT_COV + 18 * 18 == REG_OUT_PASSES && REG_OUT_TICKET == REG_OUT_DOUBLES - 1, "registration result block layout");
 
 void launch_residual(hipStream_t s, const RegMapDev& m, const RegIterArgs& a, RegState* rs, const float* pts, int n, double* partials, unsigned int* done_counter,
                      double* out48, double* reg_out, double ticket, int8_t* o_match, int32_t* o_node, float* o_dis, double* o_rinv, double* o_normal);
@@ -84,7 +99,8 @@ void launch_point_var(hipStream_t s, const RegMapDev& m, const ScanParams& sp, c
                       unsigned long long* sort_key, uint32_t* slot, int32_t* pt_next, const float* raw_xyzi = nullptr, float* world_xyzi = nullptr, int n_raw = 0);
 // (raw_xyzi != nullptr: the same launch also transforms the full xyzI scan into the world frame for the mesher)
 void launch_replay_lists(hipStream_t s, const RegMapDev& m, const int32_t* pt_next, const unsigned long long* sort_key, const double* pt_data, int n,
-                         int64_t* stats, int32_t* host_counters, int32_t* big_idx, int32_t* big_order, uint32_t* general_list, unsigned long long* dbg = nullptr, bool with_tail = true, unsigned long long* flag_dev = nullptr, unsigned long long* flag_host = nullptr, unsigned long long flag_seq = 0);
+                         int64_t* stats, int32_t* host_counters, int32_t* big_idx, int32_t* big_order, uint32_t* general_list, unsigned long long* dbg, bool with_tail, unsigned long long* flag_dev, unsigned long long* flag_host, unsigned long long flag_seq,
+                         int fused_wgs, int list_div_knob);   // (the last two: Knobs::fused_wgs / Knobs::list_div of the caller's context)
 // the tail of a map update whose launch was deferred (launch_replay_lists with_tail = false; RegIterArgs::pad of the next residual_persistent_kernel)
 void launch_map_update_tail(hipStream_t s, const RegMapDev& m, int32_t* host_counters);
 void launch_segment_heads(hipStream_t s, const uint32_t* sorted_slot, int n, int32_t* seg_start, int32_t* nseg);

@@ -8,7 +8,6 @@
 #include <cmath>
 #include <functional>
 
-static int64_t np2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return p; }
 
 // worker-thread flavour of HIPCHK: the error text goes to MeshHost::err (the caller thread owns immesh_ctx::err)
 #define MHIPCHK(ctx, expr)                                                                                  \
@@ -56,7 +55,7 @@ int mesh_alloc(immesh_ctx* c) {
     A(m.cand_status, cap_cand); A(m.cand_vox, cap_cand); A(m.cand_cell, cap_cand); A(m.cand_next, cap_cand); A(m.cand_rank, cap_cand); A(m.cand_pt, cap_cand + 32768); A(m.cand_flags, cap_cand); A(m.bin_cnt, 2 * (1024 + 1));
     A(m.ch_keys, ccap); A(m.ch_head, ccap);
     A(m.recent, cap_cand);
-    int64_t cap_active_p2 = 1; while (cap_active_p2 < cap_active) cap_active_p2 <<= 1;   // mesh_append_finish_kernel's ordering network pads to a power of two
+    const int64_t cap_active_p2 = np2(cap_active);   // mesh_append_finish_kernel's ordering network pads to a power of two
     A(m.act_key, cap_active_p2); A(m.act_vox, cap_active_p2); A(m.act_key_s, cap_active); A(m.act_vox_s, cap_active);
     A(m.rel_ids, cap_active * MV_REL_CAP); A(m.rel_n, cap_active); A(m.rel_nq, cap_active);
     A(m.vox_tris, cap_active * 2 * MV_REL_CAP); A(m.vox_ntris, cap_active);
@@ -97,7 +96,7 @@ int mesh_alloc(immesh_ctx* c) {
     m.min_spacing = g.mesh_min_spacing; m.voxel = g.mesh_voxel; m.accept = g.mesh_voxel * 1.25;
     m.shard_rank = shard_mesh ? g.shard_rank : 0; m.shard_world = shard_mesh ? g.shard_world : 1; m.shard_brick_log2 = g.shard_brick_log2 > 0 ? g.shard_brick_log2 : 5; m.shard_scheme = g.shard_scheme == 1 ? 1 : 0;
     m.dbg = nullptr;
-    if (getenv("IMMESH_DEBUG")) { unsigned long long* t; if ((rc = c->dalloc(&t, 64))) return rc; m.dbg = t; (void)hipMemset(t, 0, 512); }
+    if (c->knobs.debug) { unsigned long long* t; if ((rc = c->dalloc(&t, 64))) return rc; m.dbg = t; (void)hipMemset(t, 0, 512); }
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemsetAsync(m.g_ent, 0xFF, (size_t)gcap * sizeof(MeshGridEnt), s));   // (key == ~0: empty)
     HIPCHK(c, hipMemsetAsync(m.x_ent, 0xFF, (size_t)xcap * sizeof(MeshVoxEnt), s));   // (key == ~0: empty, val == -1)
@@ -119,12 +118,7 @@ int mesh_alloc(immesh_ctx* c) {
     }
     for (int k = 0; k < MESH_NPAR; k++) {
         MeshDyn* t; if ((rc = c->dalloc(&t, 1))) return rc; h.d_dyn[k] = t;
-        HIPCHK(c, hipHostMalloc((void**)&h.h_dyn[k], sizeof(MeshDyn), hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer((void**)&h.h_dyn_dev[k], h.h_dyn[k], 0));
-        std::memset(h.h_dyn[k], 0, sizeof(MeshDyn));
-        HIPCHK(c, hipHostMalloc((void**)&h.h_sc2[k], MESH_PUB_WORDS * 4, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer((void**)&h.h_sc2_dev[k], h.h_sc2[k], 0));
-        std::memset(h.h_sc2[k], 0, MESH_PUB_WORDS * 4);
+        if ((rc = c->pinned(&h.h_dyn[k], &h.h_dyn_dev[k], 1)) || (rc = c->pinned(&h.h_sc2[k], &h.h_sc2_dev[k], MESH_PUB_WORDS))) return rc;
     }
     h.h_sc = h.h_sc2[0];
     m.dyn = h.d_dyn[0];
@@ -152,39 +146,16 @@ int mesh_alloc(immesh_ctx* c) {
             w.out_own_add = o.own_add; w.out_own_rem = o.own_rem; w.out_own_upd = o.own_upd;
         }
     }
-    h.use_graph = getenv("IMMESH_NO_GRAPH") == nullptr;
-    h.split_mode = getenv("IMMESH_NO_SPLIT") ? 0 : 2;
-    if (const char* e = getenv("IMMESH_SPLIT")) h.split_mode = atoi(e) == 0 ? 0 : 1;
-    h.room = 0;   // 0: the worker decides (two jobs in flight; three, with the triangulations on the third stream, while the mesher is behind)
-    if (const char* e = getenv("IMMESH_MESH_ROOM")) h.room = std::min(std::max(atoi(e), 1), MESH_NPAR);   // (measurement knob: a fixed number of jobs in flight; 2 = rounds 1-5)
-    h.pipeline = getenv("IMMESH_NO_PIPELINE") == nullptr;
     HIPCHK(c, hipHostMalloc((void**)&h.h_pc, PC_COUNT * 4));
     std::memset(h.h_pc, 0, PC_COUNT * 4);
     HIPCHK(c, hipStreamSynchronize(s));
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    if (getenv("IMMESH_NO_PRIORITY")) prio_least = 0;
-    {
-        // The mesher's two streams are plain non-blocking streams of the lowest priority.  IMMESH_MESH_CUS=n confines them to n CUs instead
-        // (hipExtStreamCreateWithCUMask).  Round 1 ran with 160 of 256 CUs by default (+16 % when the mesher's lone wavefronts slowed the pose
-        // chain's kernels); with the round-2 kernels the gain is within noise (3280 vs 3220 scans/s), and CU-masked streams are BLOCKING streams
-        // on which event-timed launches failed intermittently (garbage counters / memory faults / hangs with the in-library profiler on,
-        // tools/debug_profiler.sh) -- so the mask is opt-in.
-        int ncu = 0;
-        if (const char* e = getenv("IMMESH_MESH_CUS")) ncu = atoi(e);
-        if (ncu >= 8 && ncu < 1024) {
-            uint32_t mask[32];
-            std::memset(mask, 0, sizeof(mask));
-            for (int i = 0; i < ncu; i++) mask[i >> 5] |= 1u << (i & 31);
-            HIPCHK(c, hipExtStreamCreateWithCUMask(&h.stream, 32, mask));
-            HIPCHK(c, hipExtStreamCreateWithCUMask(&h.stream_b, 32, mask));
-        } else {
-            HIPCHK(c, hipStreamCreateWithPriority(&h.stream, hipStreamNonBlocking, prio_least));
-            HIPCHK(c, hipStreamCreateWithPriority(&h.stream_b, hipStreamNonBlocking, prio_least));
-        }
-        HIPCHK(c, hipStreamCreateWithPriority(&h.stream_fetch, hipStreamNonBlocking, prio_least));
-        h.stream_q = h.stream_fetch;   // (no HSA queue of its own: an extra queue in the process costs every stream -- immesh_create; queries and fetches are both rare and short)
-    }
+    // The mesher's two streams are plain non-blocking streams of the lowest priority; IMMESH_MESH_CUS=n confines them to n CUs instead (Knobs::make_stream).
+    // Round 1 ran with 160 of 256 CUs by default (+16 % when the mesher's lone wavefronts slowed the pose chain's kernels); with the round-2 kernels the
+    // gain is within noise (3280 vs 3220 scans/s)
+    HIPCHK(c, c->knobs.make_stream(&h.stream, c->prio_least, true));
+    HIPCHK(c, c->knobs.make_stream(&h.stream_b, c->prio_least, true));
+    HIPCHK(c, c->knobs.make_stream(&h.stream_fetch, c->prio_least, false));
+    h.stream_q = h.stream_fetch;   // (no HSA queue of its own: an extra queue in the process costs every stream -- immesh_create; queries and fetches are both rare and short)
     for (int k = 0; k < MESH_WORLD_BUFS; k++) HIPCHK(c, hipEventCreateWithFlags(&h.ev_ready[k], hipEventDisableTiming));
     for (int k = 0; k < MESH_NPAR; k++) {
         HIPCHK(c, hipEventCreateWithFlags(&h.ev_a[k], hipEventDisableTiming));
@@ -220,9 +191,10 @@ static void mesh_print_marks(const MeshHost& h) {
     fprintf(stderr, " | end-to-end %.1f us, previous job's end -> phase B's first kernel %.1f us | scan thread's wait for a world buffer %.1f us (last %lld scans)\n", period / (double)n, bgap / (double)n, nw ? w / (double)nw : 0.0, nw);
 }
 void mesh_free(immesh_ctx* c) {
-    if (getenv("IMMESH_DEBUG_WAITS")) mesh_print_marks(c->mesh_host);
-    if (getenv("IMMESH_DEBUG_WAITS") && c->mesh_host.wait_calls) fprintf(stderr, "[mesh] scan thread waited for a world buffer: %.1f us per scan over %lld scans\n", 1e-3 * (double)c->mesh_host.wait_ns / (double)c->mesh_host.wait_calls, c->mesh_host.wait_calls);
-    if (getenv("IMMESH_DEBUG_WAITS") && c->mesh_host.job_ms_n) fprintf(stderr, "[mesh] device time per job (begin_scan's poll answered -> publish): %.1f us over %lld jobs\n", 1e3 * c->mesh_host.job_ms_sum / (double)c->mesh_host.job_ms_n, c->mesh_host.job_ms_n);
+    const bool dbg_waits = c->knobs.debug_waits;
+    if (dbg_waits) mesh_print_marks(c->mesh_host);
+    if (dbg_waits && c->mesh_host.wait_calls) fprintf(stderr, "[mesh] scan thread waited for a world buffer: %.1f us per scan over %lld scans\n", 1e-3 * (double)c->mesh_host.wait_ns / (double)c->mesh_host.wait_calls, c->mesh_host.wait_calls);
+    if (dbg_waits && c->mesh_host.job_ms_n) fprintf(stderr, "[mesh] device time per job (begin_scan's poll answered -> publish): %.1f us over %lld jobs\n", 1e3 * c->mesh_host.job_ms_sum / (double)c->mesh_host.job_ms_n, c->mesh_host.job_ms_n);
     MeshHost& h = c->mesh_host;
     if (h.worker.joinable()) {
         { std::lock_guard<std::mutex> lk(h.mu); h.stop = true; }
@@ -252,9 +224,6 @@ void mesh_free(immesh_ctx* c) {
         if (h.ev_b[k]) (void)hipEventDestroy(h.ev_b[k]);
         if (h.graph_exec[k]) { (void)hipGraphExecDestroy(h.graph_exec[k]); h.graph_exec[k] = nullptr; }
         for (int q = 0; q < 2; q++) if (h.graph_exec_b[k][q]) { (void)hipGraphExecDestroy(h.graph_exec_b[k][q]); h.graph_exec_b[k][q] = nullptr; }
-        if (h.h_dyn[k]) (void)hipHostFree(h.h_dyn[k]);
-        if (h.h_sc2[k]) (void)hipHostFree(h.h_sc2[k]);
-        h.h_dyn[k] = nullptr; h.h_sc2[k] = nullptr;
     }
     if (h.h_pc) (void)hipHostFree(h.h_pc);
     h.h_sc = h.h_pc = nullptr;
@@ -297,14 +266,14 @@ static int mesh_enqueue_a(immesh_ctx* c, const MeshDev& m, int par, hipStream_t 
         // correct_triangle_index, which voxel's flip wins): the deterministic sequential order of the CPU checker
         launch_mesh_sort_emit(s, m, 0, h.d_sort_recs_a, nullptr);   // sorted active list + ranks
     }
-    launch_mesh_knn(s, m);                                      // a18-a19
+    launch_mesh_knn(s, m, c->knobs.mesh_grid_div);                                   // a18-a19
     return 0;
 }
 // Phase B: a20-a24 (triangulation, diff against the live set, commit: all removes, then all adds -- ImMesh_mesh_reconstruction.cpp:228-244;
 // result lists sorted by triplet), then the counters go to the host.
 static int mesh_enqueue_b(immesh_ctx* c, const MeshDev& m, int par, hipStream_t s, int part = 0, bool split = false) {   // part 1: triangulation only, 2: the rest
     MeshHost& h = c->mesh_host;                                // split: the triangulations ran on the third stream (mesh_tri64_kernel): only the diff is left
-    if (part != 2) { if (split) launch_mesh_diff64(s, m); else launch_mesh_delaunay(s, m); }   // a20-a23
+    if (part != 2) { if (split) launch_mesh_diff64(s, m, c->knobs.mesh_grid_div); else launch_mesh_delaunay(s, m, c->knobs.mesh_grid_div); }   // a20-a23
     if (part == 1) return 0;
     launch_mesh_finalize(s, m);                               // (+ the removals: Triangle_manager::remove_triangle_list)
     launch_mesh_sort_emit(s, m, 1, h.d_sort_recs, h.p_a);
@@ -482,7 +451,7 @@ static int mesh_scan_launch(immesh_ctx* c, const MeshJob& job, bool& synced, boo
             if (h.h_sc2[par][SC_UNDECIDED] == 0) break;
         }
         if ((rc = mesh_enqueue_a(c, m, par, sa, d_pts, sp.n_cand, ccap, false))) return rc;
-    } else if (h.use_graph && !h.prof.on && is_world) {
+    } else if (!c->knobs.no_graph && !h.prof.on && is_world) {
         // steady state: the launches of a phase are captured once per (parity, candidate count) and replayed as one hipGraph
         if (h.graph_ncand[par] != n_key) {
             for (hipGraphExec_t* e : {&h.graph_exec[par], &h.graph_exec_b[par][0], &h.graph_exec_b[par][1]}) if (*e) { (void)hipGraphExecDestroy(*e); *e = nullptr; }
@@ -503,19 +472,19 @@ static int mesh_scan_launch(immesh_ctx* c, const MeshJob& job, bool& synced, boo
     // chain (~3 us per scan) and ~15 us of job latency (two cross-stream events).  That pays while the mesher is what the pipeline waits for and costs
     // 1.7 % where it is not (the driver's 20-scan run on a young map: the pose chain is slower than even the one-launch phase B).  The worker therefore
     // switches: `deep` = a job found another one queued behind it within the last 64 jobs (mesh_worker_main).  IMMESH_SPLIT = 1 / 0: always / never.
-    const bool split = n_key <= 65536 && (h.split_mode == 1 || (h.split_mode == 2 && deep));
+    const bool split = n_key <= 65536 && (c->knobs.split_mode == 1 || (c->knobs.split_mode == 2 && deep));
     if (split) {
-        static const int which = [] { const char* e = getenv("IMMESH_TRI_STREAM"); return e ? atoi(e) : 1; }();   // (measurement knob: 0 fetch stream, 1 pre-processing stream (default), 2 null stream)
+        const int which = c->knobs.tri_stream;   // (measurement knob: 0 fetch stream, 1 pre-processing stream (default), 2 null stream)
         hipStream_t st = which == 1 ? c->stream_pre : (which == 2 ? (hipStream_t)nullptr : h.stream_fetch);
         MHIPCHK(c, hipStreamWaitEvent(st, h.ev_a[par], 0));
-        launch_mesh_tri64(st, m);
+        launch_mesh_tri64(st, m, c->knobs.mesh_grid_div);
         MHIPCHK(c, hipEventRecord(h.ev_c[par], st));
         MHIPCHK(c, hipStreamWaitEvent(sb, h.ev_c[par], 0));
     } else MHIPCHK(c, hipStreamWaitEvent(sb, h.ev_a[par], 0));
-    if (h.use_graph && !h.prof.on && n_key <= 65536 && is_world) {
+    if (!c->knobs.no_graph && !h.prof.on && n_key <= 65536 && is_world) {
         // (both variants of phase B are captured when the first of them is needed: instantiating a graph takes a millisecond, and the switch to the other
         //  arrangement must not pay it in the middle of a stream)
-        if (h.graph_exec_b[par][split ? 0 : 1] == nullptr && h.split_mode == 2 &&
+        if (h.graph_exec_b[par][split ? 0 : 1] == nullptr && c->knobs.split_mode == 2 &&
             (rc = mesh_graph_run(c, h.graph_exec_b[par][split ? 0 : 1], sb, [&] { return mesh_enqueue_b(c, m, par, sb, 0, !split); }, false))) return rc;
         if ((rc = mesh_graph_run(c, h.graph_exec_b[par][split ? 1 : 0], sb, [&] { return mesh_enqueue_b(c, m, par, sb, 0, split); }))) return rc;
     } else {
@@ -567,7 +536,7 @@ static int mesh_scan_finish(immesh_ctx* c, const MeshJob& job, immesh_mesh_sizes
         fprintf(stderr, "[delaunay cycles/voxel] load %llu pca+proj %llu sort %llu insert %llu filter %llu oldset %llu adds %llu\n", t[0] / std::max(1, n_active), t[1] / std::max(1, n_active),
                 t[2] / std::max(1, n_active), t[3] / std::max(1, n_active), t[4] / std::max(1, n_active), t[5] / std::max(1, n_active), t[6] / std::max(1, n_active));
     }
-    if (getenv("IMMESH_DEBUG")) fprintf(stderr, "[mesh] cand %d new %d active %d maxnu %d pass2 %d add %d rem %d\n", n_cand, n_new, n_active, h.h_sc[SC_MAXNU], h.h_sc[SC_PASS2], n_add, n_rem);
+    if (c->knobs.debug) fprintf(stderr, "[mesh] cand %d new %d active %d maxnu %d pass2 %d add %d rem %d\n", n_cand, n_new, n_active, h.h_sc[SC_MAXNU], h.h_sc[SC_PASS2], n_add, n_rem);
     return 0;
 }
 
@@ -582,6 +551,13 @@ static void mesh_worker_main(immesh_ctx* c) {
     long deep_until = 0;   // (job id) the deep arrangement stays on for jobs below it
     bool deep = false;
     int backlog_streak = 0;
+    // jobs the pipeline may hold in flight right now (h.mu held): three while the job at the head of the queue would run deep, else two
+    auto room = [&]() -> size_t {
+        if (c->knobs.no_pipeline || h.prof.on || c->mesh.shard_world > 1) return 1;
+        if (c->knobs.mesh_room) return (size_t)c->knobs.mesh_room;
+        const bool deep_now = c->knobs.split_mode == 1 || (c->knobs.split_mode == 2 && !h.q.empty() && h.q.front().id < deep_until);
+        return deep_now ? (size_t)MESH_NPAR : (size_t)2;
+    };
     for (;;) {
         // ---- take a new job when one is queued and the pipeline has room
         bool have = false;
@@ -589,15 +565,13 @@ static void mesh_worker_main(immesh_ctx* c) {
         {
             std::unique_lock<std::mutex> lk(h.mu);
             if (fl.empty()) h.cv_job.wait(lk, [&] { return h.stop || !h.q.empty(); });
-            const bool deep_now = h.split_mode == 1 || (h.split_mode == 2 && !h.q.empty() && h.q.front().id < deep_until);
-            const size_t room = (h.pipeline && !h.prof.on && c->mesh.shard_world <= 1) ? (h.room ? (size_t)h.room : (deep_now ? (size_t)MESH_NPAR : (size_t)2)) : 1;
-            if (!h.q.empty() && fl.size() < room) {
+            if (!h.q.empty() && fl.size() < room()) {
                 job = h.q.front(); h.q.pop_front(); have = true;
                 // the mesher is behind when a job leaves the queue and the next one is already waiting: go deep (three jobs in flight, triangulations on
                 // the third stream) for the next 64 jobs -- long enough not to flutter, short enough to fall back when the stream slows down
                 backlog_streak = h.q.empty() ? 0 : backlog_streak + 1;
                 if (backlog_streak >= 3) deep_until = job.id + 64;   // (three jobs in a row: a lag, not the hiccup of a graph capture or a first touch)
-                deep = h.split_mode == 1 || (h.split_mode == 2 && job.id < deep_until);
+                deep = c->knobs.split_mode == 1 || (c->knobs.split_mode == 2 && job.id < deep_until);
             }
             else if (fl.empty() && h.q.empty()) break;   // stop requested and nothing left to do
         }
@@ -630,7 +604,7 @@ static void mesh_worker_main(immesh_ctx* c) {
             } else q = hipEventQuery(h.ev_b[par]);
             if (q == hipErrorNotReady) {
                 bool more;
-                { std::lock_guard<std::mutex> lk(h.mu); more = !h.q.empty() && fl.size() < ((h.pipeline && !h.prof.on && c->mesh.shard_world <= 1) ? (h.room ? (size_t)h.room : ((h.split_mode == 1 || h.q.front().id < deep_until) ? (size_t)MESH_NPAR : (size_t)2)) : (size_t)1); }
+                { std::lock_guard<std::mutex> lk(h.mu); more = !h.q.empty() && fl.size() < room(); }
                 if (!more) std::this_thread::yield();
                 continue;
             }
@@ -701,7 +675,7 @@ float* mesh_next_world_buffer(immesh_ctx* c) {
     std::unique_lock<std::mutex> lk(h.mu);
     const long next = h.submitted + 1;
     // IMMESH_DEBUG_WAITS: how long the scan thread stands here = how far the mesher is behind the pose chain (printed by mesh_free)
-    static const bool dbg_waits = getenv("IMMESH_DEBUG_WAITS") != nullptr;
+    const bool dbg_waits = c->knobs.debug_waits;
     const auto t0 = dbg_waits ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     h.cv_done.wait(lk, [&] { return h.completed >= next - MESH_WORLD_BUFS && (!h.collect_on || h.collected >= next - 2); });   // (result lists: two sets, job parity)
     if (dbg_waits) { const long long w = (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); h.wait_ns += w; h.wait_ring[h.wait_calls & 63] = w; h.wait_calls++; }

@@ -41,7 +41,7 @@ IMD unsigned long long mkey(long x, long y, long z) {
            ((unsigned long long)(z + MKEY_BIAS) & MKEY_MASK);
 }
 IMD long rnd_cell(float p, double cell) { return (long)(int)round((double)p / cell); }  // std::round of the f64 quotient, pointcloud_rgbd.cpp:467-472
-// sharded mesher: mesh voxels are owned in bricks of 2^shard_brick_log2 voxels per axis; the owner function is the registration map's (regmap.hpp brick_owner)
+// sharded mesher: mesh voxels are owned in bricks of 2^shard_brick_log2 voxels per axis; the same colouring / hash as regmap.hpp brick_owner, but over the mesher's own key packing (mkey: x-major) and WITHOUT the rule for worlds divisible by 3 or 5 -- self-consistent across ranks, a partition of mesh voxels, not of map voxels
 IMD int mesh_owner_xyz(const MeshDev& m, long x, long y, long z) {
     const int b = m.shard_brick_log2;   // arithmetic shifts: bricks tile negative cells too
     if (m.shard_scheme == 1) return (int)(hash64(mkey(x >> b, y >> b, z >> b)) % (unsigned long long)m.shard_world);
@@ -2167,8 +2167,8 @@ void launch_mesh_append_flags(hipStream_t s, const MeshDev& m, int n_cand) { KLA
 void launch_mesh_select_active(hipStream_t s, const MeshDev& m, int n_cand) { KLAUNCH(mesh_select_active_kernel, g1(n_cand), dim3(256), 0, s, m); }
 // IMMESH_MESH_GRID_DIV (experiments): divides the grids of the two big per-voxel kernels -- fewer resident mesher wavefronts per SIMD leave register
 // room for the registration chain's kernels
-static int mesh_grid_div() { static const int v = getenv("IMMESH_MESH_GRID_DIV") ? std::max(1, atoi(getenv("IMMESH_MESH_GRID_DIV"))) : 1; return v; }
-void launch_mesh_knn(hipStream_t s, const MeshDev& m) { KLAUNCH(mesh_knn_kernel<false>, dim3(512 / mesh_grid_div()), dim3(256), 0, s, m, (float*)nullptr, 1.0, (const int32_t*)nullptr, 0, (double*)nullptr, 0.0); }
+// grid_div (>= 1): Knobs::mesh_grid_div of the caller's context
+void launch_mesh_knn(hipStream_t s, const MeshDev& m, int grid_div) { KLAUNCH(mesh_knn_kernel<false>, dim3(512 / grid_div), dim3(256), 0, s, m, (float*)nullptr, 1.0, (const int32_t*)nullptr, 0, (double*)nullptr, 0.0); }
 void launch_mesh_export_vertices(hipStream_t s, const MeshDev& m, float* export_vtx, double smooth_factor) {
     KLAUNCH(mesh_knn_kernel<true>, dim3(2048), dim3(256), 0, s, m, export_vtx, smooth_factor, (const int32_t*)nullptr, 0, (double*)nullptr, 0.0);
 }
@@ -2237,15 +2237,15 @@ void launch_mesh_export_keys(hipStream_t s, const MeshDev& m, const int32_t* tri
     KLAUNCH(mesh_export_keys_kernel, g1(n), dim3(256), 0, s, m, tris, n, which, k32, k64);
 }
 void launch_mesh_export_wind(hipStream_t s, const MeshDev& m, const int32_t* tri_sorted, int n, int32_t* faces) { KLAUNCH(mesh_export_wind_kernel, g1(n), dim3(256), 0, s, m, tri_sorted, n, faces); }
-void launch_mesh_delaunay(hipStream_t s, const MeshDev& m) {
+void launch_mesh_delaunay(hipStream_t s, const MeshDev& m, int grid_div) {
     // (grids: the dispatcher places ~130 workgroups per us, so a launch of 2048 workgroups lasts >= 16 us however little they do; the kernels stride)
-    KLAUNCH(mesh_delaunay64_kernel<0>, dim3(768 / mesh_grid_div()), dim3(64), 0, s, m);           // n_u <= 64: register fast path
+    KLAUNCH(mesh_delaunay64_kernel<0>, dim3(768 / grid_div), dim3(64), 0, s, m);           // n_u <= 64: register fast path
     KLAUNCH(mesh_delaunay_general_kernel, dim3(MV_GEN_BLOCKS), dim3(64), 0, s, m);     // 64 < n_u and what the fast path handed over
 }
 // the same in two launches on two streams (mesh_delaunay64.inc): the triangulations behind phase A, the diff against the live set at the head of phase B
-void launch_mesh_tri64(hipStream_t s, const MeshDev& m) { KLAUNCH(mesh_tri64_kernel, dim3(768 / mesh_grid_div()), dim3(64), 0, s, m); }
-void launch_mesh_diff64(hipStream_t s, const MeshDev& m) {
-    KLAUNCH(mesh_diff64_kernel, dim3(768 / mesh_grid_div()), dim3(64), 0, s, m);
+void launch_mesh_tri64(hipStream_t s, const MeshDev& m, int grid_div) { KLAUNCH(mesh_tri64_kernel, dim3(768 / grid_div), dim3(64), 0, s, m); }
+void launch_mesh_diff64(hipStream_t s, const MeshDev& m, int grid_div) {
+    KLAUNCH(mesh_diff64_kernel, dim3(768 / grid_div), dim3(64), 0, s, m);
     KLAUNCH(mesh_delaunay_general_kernel, dim3(MV_GEN_BLOCKS), dim3(64), 0, s, m);
 }
 void launch_mesh_finalize(hipStream_t s, const MeshDev& m) { KLAUNCH(mesh_finalize_kernel, dim3(128), dim3(64), 0, s, m); }

@@ -184,10 +184,6 @@ struct MeshHost {
     hipGraphExec_t graph_exec[MESH_NPAR] = {};   // phase A, one per job parity (world buffer / result set pointers differ)
     hipGraphExec_t graph_exec_b[MESH_NPAR][2] = {}; // phase B ([1]: without the triangulations)
     int graph_ncand[MESH_NPAR] = {-1, -1, -1};           // candidate count the graph was captured for (grid sizes, clear sizes)
-    bool use_graph = true;
-    int room = 0;            // jobs the worker keeps in flight: 0 = two, three while the mesher is behind (mesh_worker_main); IMMESH_MESH_ROOM fixes it
-    int split_mode = 2;      // the triangulations on the third stream, the diff at the head of phase B: 0 never (IMMESH_NO_SPLIT / IMMESH_SPLIT=0), 1 always (IMMESH_SPLIT=1), 2 while the mesher is behind (with the third job in flight)
-    bool pipeline = true;                    // phase A of scan k+1 may overlap phase B of scan k (IMMESH_NO_PIPELINE turns it off)
     // mesh export scratch (grow-only)
     void *exp_vtx = nullptr, *exp_work = nullptr, *exp_tmp = nullptr;
     size_t exp_vtx_bytes = 0, exp_work_bytes = 0, exp_tmp_bytes = 0;
@@ -226,7 +222,7 @@ void launch_mesh_append_commit(hipStream_t s, const MeshDev& m, int n_cand, cons
 void launch_mesh_append_flags(hipStream_t s, const MeshDev& m, int n_cand);
 void launch_mesh_select_active(hipStream_t s, const MeshDev& m, int n_cand);
 void launch_mesh_append_finish(hipStream_t s, const MeshDev& m, const float* pts);   // flags + scan + commit + select + active-voxel order in one launch (n_cand <= 16384)
-void launch_mesh_knn(hipStream_t s, const MeshDev& m);
+void launch_mesh_knn(hipStream_t s, const MeshDev& m, int grid_div);
 void launch_mesh_export_vertices(hipStream_t s, const MeshDev& m, float* export_vtx, double smooth_factor);
 void launch_mesh_query_voxels(hipStream_t s, const MeshDev& m, const int32_t* ids, int n, int n_vertices, int display, int32_t* vox_out);
 void launch_mesh_query_smooth(hipStream_t s, const MeshDev& m, const int32_t* vox_list, int n_list, double smooth_factor, double max_dis, double* export_d);
@@ -234,9 +230,9 @@ void launch_mesh_query_gather(hipStream_t s, const MeshDev& m, const int32_t* id
 void launch_mesh_export_faces(hipStream_t s, const MeshDev& m, int32_t* tri_idx, int32_t* count);
 void launch_mesh_export_keys(hipStream_t s, const MeshDev& m, const int32_t* tris, int n, int which, uint32_t* k32, unsigned long long* k64);
 void launch_mesh_export_wind(hipStream_t s, const MeshDev& m, const int32_t* tri_sorted, int n, int32_t* faces);
-void launch_mesh_delaunay(hipStream_t s, const MeshDev& m);
-void launch_mesh_tri64(hipStream_t s, const MeshDev& m);
-void launch_mesh_diff64(hipStream_t s, const MeshDev& m);
+void launch_mesh_delaunay(hipStream_t s, const MeshDev& m, int grid_div);
+void launch_mesh_tri64(hipStream_t s, const MeshDev& m, int grid_div);
+void launch_mesh_diff64(hipStream_t s, const MeshDev& m, int grid_div);
 void launch_mesh_finalize(hipStream_t s, const MeshDev& m);
 // exchange blocks of the sharded mesher: every rank contributes ONE fixed-size block per exchange -- 16-byte header {records, aux, -, -} + records -- so an
 // exchange is a single all-gather, and the unpack kernels read the counts on the device (cap_rec = records a block holds)

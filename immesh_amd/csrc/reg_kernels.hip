@@ -467,7 +467,7 @@ __device__ __forceinline__ bool ekf_step_wave(RegState* __restrict__ rs, const d
 #pragma unroll
             for (int k = 0; k < 6; k++) sub += g6[k] * c6[k];
             const double sacc = cov[e] - sub;
-            __hip_atomic_store((unsigned long long*)&reg_out[24 + e], (unsigned long long)__double_as_longlong(sacc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_COV + e], (unsigned long long)__double_as_longlong(sacc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (r < 3 && c < 3) rs->sp.rot_var[r * 3 + c] = sacc;                       // the map update propagates the POSTERIOR covariance blocks
             if (r >= 3 && r < 6 && c >= 3 && c < 6) rs->sp.t_var[(r - 3) * 3 + (c - 3)] = sacc;
         }
@@ -475,24 +475,21 @@ __device__ __forceinline__ bool ekf_step_wave(RegState* __restrict__ rs, const d
             double v = 0;
 #pragma unroll
             for (int k = 0; k < 24; k++) if (lane == k) v = st[k];
-            __hip_atomic_store((unsigned long long*)&reg_out[lane], (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_STATE + lane], (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (lane == 0) {
             const double o[6] = {passes, n_match, res_sum, C[156], C[157], C[159]};
-            for (int k = 0; k < 6; k++) __hip_atomic_store((unsigned long long*)&reg_out[348 + k], (unsigned long long)__double_as_longlong(o[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            for (int k = 0; k < 6; k++) __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_PASSES + k], (unsigned long long)__double_as_longlong(o[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (lane == 0) __hip_atomic_store(&reg_out[REG_OUT_DOUBLES - 1], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (lane == 0) __hip_atomic_store(&reg_out[REG_OUT_TICKET], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     EDBG(4);
     if (dbg && lane == 0) dbg[47] += 1;
 #undef EDBG
     return stop;
 }
-
-#define RES_NV 48   // host layout: 36 HTH + 6 HTz + n_match + sum|dis| + n_plane_tests + n_extra_probe + 2 spare
-#define RES_NR 32   // reduced per block: 21 (upper triangle of HTH) + 6 HTz + 4 counters + 1 spare
 
 
 // One point of one residual pass: transformLidar + covariance propagation (lio_state_estimation :1302-1359), BuildResidualListOMP with the
@@ -767,7 +764,7 @@ __global__ __launch_bounds__(64) void residual_kernel(RegMapDev m, RegIterArgs a
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // slot 47 is the completion ticket the host polls: a release store, issued after the 47 value stores of this (single) wavefront drained
     RDBG(5);
-    if (lane == 0 && a.mode == REG_MODE_HOST) __hip_atomic_store(&out48[RES_NV - 1], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (lane == 0 && a.mode == REG_MODE_HOST) __hip_atomic_store(&out48[RES_TICKET], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -795,7 +792,6 @@ __global__ __launch_bounds__(64) void residual_kernel(RegMapDev m, RegIterArgs a
 // ---------------------------------------------------------------------------------------------------------------------
 #define RP_MAX_BLOCKS 128
 #define RP_SPIN_TICKS 100000000ull   /* 1 s */
-#define RP_SENTINEL 0x7FF8DEADBEEF0001ull
 static_assert(COOP_WORDS * 4 <= RES_NR * 65 * 8, "the cooperative matcher's scratch lives in a wavefront's reduction transpose buffer");
 struct RpShared {
     double red[4][RES_NR][65];   // per-wavefront transposes
@@ -846,7 +842,7 @@ __device__ __forceinline__ void rp_update(RpShared& S, const RegIterArgs& a, con
     double hrow[6], trow[6];
 #pragma unroll
     for (int c = 0; c < 6; c++) { hrow[c] = S.sums[row * 6 + c]; trow[c] = S.pc[36 + (own >= 6 ? own - 6 : 0) * 6 + c]; }
-    const double hz = S.sums[36 + row];
+    const double hz = S.sums[RES_HTZ + row];
     const double st_own = S.st[own + 6], prior_own = S.prior[own + 6];     // (components 3..17 of vec are plain differences)
     // ---- w = H^T z - H^T H vec6 (lanes 6..11), broadcast
     double w[6];
@@ -913,7 +909,7 @@ __device__ __forceinline__ void rp_update(RpShared& S, const RegIterArgs& a, con
     int rematch = S.rematch;
     if (converged || ((rematch == 0) && (it == (a.max_iter - 2)))) rematch++;
     const bool stop = rematch >= 2 || (it == a.max_iter - 1);
-    const double t_tests = S.tot[0] + S.sums[44], t_extra = S.tot[1] + S.sums[45], t_pass = S.tot[2] + 1.0, t_match = S.tot[3] + S.sums[42];
+    const double t_tests = S.tot[0] + S.sums[RES_PLANE_TESTS], t_extra = S.tot[1] + S.sums[RES_EXTRA_PROBE], t_pass = S.tot[2] + 1.0, t_match = S.tot[3] + S.sums[RES_N_MATCH];
     if (lane >= 6 && lane < 18) S.st[lane + 6] = st_own + sol_own;
     if (lane == 0) {
 #pragma unroll
@@ -970,14 +966,14 @@ __device__ __forceinline__ void rp_finish(RpShared& S, const RegIterArgs& a, Reg
             for (int k = 0; k < 6; k++) upd += S.pc[36 + (r - 6) * 6 + k] * S.XM[k * 18 + c];
         }
         const double sacc = cov[e] - upd;
-        __hip_atomic_store((unsigned long long*)&reg_out[24 + e], (unsigned long long)__double_as_longlong(sacc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_COV + e], (unsigned long long)__double_as_longlong(sacc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (r < 3 && c < 3) rs->sp.rot_var[r * 3 + c] = sacc;                       // the map update propagates the POSTERIOR covariance blocks
         if (r >= 3 && r < 6 && c >= 3 && c < 6) rs->sp.t_var[(r - 3) * 3 + (c - 3)] = sacc;
     }
     if (tid < 24) {
         const double v = S.st[tid];
         rs->st[tid] = v;
-        __hip_atomic_store((unsigned long long*)&reg_out[tid], (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_STATE + tid], (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (tid < 9) {
             rs->sp.R[tid] = v;
             const int r = tid / 3, c = tid % 3;
@@ -986,12 +982,12 @@ __device__ __forceinline__ void rp_finish(RpShared& S, const RegIterArgs& a, Reg
     }
     if (tid == 64) {
         rs->rematch = S.rematch; rs->done = 1;
-        const double o[6] = {S.tot[2], S.sums[42], S.sums[43], S.tot[0], S.tot[1], S.tot[3]};
-        for (int k = 0; k < 6; k++) __hip_atomic_store((unsigned long long*)&reg_out[348 + k], (unsigned long long)__double_as_longlong(o[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const double o[6] = {S.tot[2], S.sums[RES_N_MATCH], S.sums[RES_SUM_DIS], S.tot[0], S.tot[1], S.tot[3]};
+        for (int k = 0; k < 6; k++) __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_PASSES + k], (unsigned long long)__double_as_longlong(o[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) __hip_atomic_store(&reg_out[REG_OUT_DOUBLES - 1], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (tid == 0) __hip_atomic_store(&reg_out[REG_OUT_TICKET], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 template <bool COOP>   // (see residual_kernel)
@@ -1008,9 +1004,9 @@ __global__ __launch_bounds__(256) void residual_persistent_kernel(RegMapDev m, R
     unsigned long long tprev = sp.dbg ? __builtin_readcyclecounter() : 0;
     const unsigned long long t_entry = sp.dbg ? __builtin_amdgcn_s_memrealtime() : 0;   // (trace: [4] of the pass-0 record = kernel entry, [5] = block 0 finished)
     // re-arm the other parity's slots for the next scan (fire-and-forget: the kernel boundary publishes them)
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < n_slots_next; e += gridDim.x * 256) ((unsigned long long*)slots_next)[e] = RP_SENTINEL;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n_slots_next; e += gridDim.x * 256) ((unsigned long long*)slots_next)[e] = RP_SLOT_SENTINEL;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ((unsigned long long*)slots_next)[RP_TAIL_WORD] = RP_SENTINEL; ((unsigned long long*)slots_next)[RP_ABORT_WORD] = RP_SENTINEL;
+        ((unsigned long long*)slots_next)[RP_TAIL_WORD] = RP_SLOT_SENTINEL; ((unsigned long long*)slots_next)[RP_ABORT_WORD] = RP_SLOT_SENTINEL;
         // "this scan's registration is running": what the next cloud's VoxelGrid waits for (ds_gate_kernel) so that it shares the chip with this launch,
         // which does not mind, and not with the map update in front of it, which does
         __hip_atomic_store(&rs->started, (int)(long long)ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1149,11 +1145,11 @@ __global__ __launch_bounds__(256) void residual_persistent_kernel(RegMapDev m, R
                     const unsigned long long abortbits = __hip_atomic_load((const unsigned long long*)&slots[RP_ABORT_WORD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     // the part of the update that needs only the iterate runs while the first round of loads is in flight
                     if (!have_vec) { rp_prior_minus_state(S, R12, vec6); have_vec = true; }
-                    bool ok = tailbits != RP_SENTINEL;
+                    bool ok = tailbits != RP_SLOT_SENTINEL;
 #pragma unroll
-                    for (int u = 0; u < 32; u++) { ok = ok && bits[u] != RP_SENTINEL; v[u] = __longlong_as_double((long long)bits[u]); }
+                    for (int u = 0; u < 32; u++) { ok = ok && bits[u] != RP_SLOT_SENTINEL; v[u] = __longlong_as_double((long long)bits[u]); }
                     // (a.pad & 2: the test hook -- every block gives up in its first poll, as if the grid had not become resident)
-                    if (__any(abortbits != RP_SENTINEL) || (a.pad & 2)) { aborted = true; break; }
+                    if (__any(abortbits != RP_SLOT_SENTINEL) || (a.pad & 2)) { aborted = true; break; }
                     if (__all(ok)) break;
                     // bounded: the slots of a block that is not resident never arrive (see the header comment)
                     if ((++spins & 63u) == 0) {
@@ -1190,9 +1186,9 @@ __global__ __launch_bounds__(256) void residual_persistent_kernel(RegMapDev m, R
         if (S.stop == 2) {
             // aborted: nothing of the scan has been written (no epilogue); every aborting block stores the same words
             if (threadIdx.x == 0) {
-                __hip_atomic_store((unsigned long long*)&reg_out[348], (unsigned long long)__double_as_longlong(-1.0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store((unsigned long long*)&reg_out[REG_OUT_PASSES], (unsigned long long)__double_as_longlong(-1.0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&reg_out[REG_OUT_DOUBLES - 1], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(&reg_out[REG_OUT_TICKET], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             break;
         }
@@ -1271,9 +1267,9 @@ __global__ __launch_bounds__(64) void ekf_step_kernel(RegIterArgs a, RegState* r
         for (int e = lane; e < (int)(sizeof(ScanParams) / 8); e += 64) dst[e] = src[e];
     }
     __syncthreads();
-    if (lane == 0) { L[400 + 156] += L[64 + 44]; L[400 + 157] += L[64 + 45]; L[400 + 159] += L[64 + 42]; }
+    if (lane == 0) { L[400 + 156] += L[64 + RES_PLANE_TESTS]; L[400 + 157] += L[64 + RES_EXTRA_PROBE]; L[400 + 159] += L[64 + RES_N_MATCH]; }
     __syncthreads();
-    ekf_step_wave(rs, L + 400, a.mat, L + 64, L + 64 + 36, L[64 + 42], L[64 + 43], L + 128, lane, a.it, a.max_iter, a.sp.extR, reg_out, ticket);
+    ekf_step_wave(rs, L + 400, a.mat, L + 64 + RES_HTH, L + 64 + RES_HTZ, L[64 + RES_N_MATCH], L[64 + RES_SUM_DIS], L + 128, lane, a.it, a.max_iter, a.sp.extR, reg_out, ticket);
 }
 
 // =====================================================================================================================
@@ -2007,7 +2003,7 @@ __global__ __launch_bounds__(256) void replay_kernel(RegMapDev m, const uint32_t
 #define DBG_FUSED_OFF 64          /* IMMESH_DEBUG buffer: [0,64) counters, then 16384 x 8 trace words of replay_fused_kernel, then 8 x 512 x 8 of the residual passes */
 #define DBG_FUSED_RECS 16384
 #define DBG_RES_OFF (DBG_FUSED_OFF + DBG_FUSED_RECS * 8)
-#define DBG_TOTAL_WORDS (DBG_RES_OFF + 8 * 512 * 8)
+static_assert(DBG_RES_OFF + 8 * 512 * 8 == REG_DBG_WORDS, "the IMMESH_DEBUG buffer (kernels.hpp) holds the counters and both trace areas");
 #define RF_PTS 128   /* a settled root's retained points + this scan's points live in registers (two per lane) */
 // ---- the map update in two launches ---------------------------------------------------------------------------------------------------------
 //   replay_fused_kernel   one wavefront per touched root voxel.  The common state of a settled map -- an initialised, planar, update-enabled root
@@ -2532,15 +2528,13 @@ void launch_point_var(hipStream_t s, const RegMapDev& m, const ScanParams& sp, c
 }
 void launch_replay_lists(hipStream_t s, const RegMapDev& m, const int32_t* pt_next, const unsigned long long* sort_key, const double* pt_data, int n,
                          int64_t* stats, int32_t* host_counters, int32_t* big_idx, int32_t* big_order, uint32_t* general_list, unsigned long long* dbg, bool with_tail,
-                         unsigned long long* flag_dev, unsigned long long* flag_host, unsigned long long flag_seq) {
-    static const int fused_wgs = [] { const char* e = getenv("IMMESH_FUSED_WGS"); const int v = e ? atoi(e) : 0; return v >= 32 ? v : 768; }();   // (measurement knob, tools/r06_fused.sh)
+                         unsigned long long* flag_dev, unsigned long long* flag_host, unsigned long long flag_seq, int fused_wgs, int list_div_knob) {
     KLAUNCH(replay_fused_kernel, dim3(std::min((n + 3) / 4, fused_wgs)), dim3(256), 0, s, m, pt_next, sort_key, pt_data, stats, general_list, dbg, flag_dev, flag_host, flag_seq);
     // the work list's length is only known on the device: a fixed grid strides over it (sized for the map-building case, where every touched voxel is on it)
     // points per workgroup of the list kernel's grid.  Two-layer maps (avia.yaml): 128 -- its ~1 100 general voxels are bound by the slowest voxel's chain, more
     // workgroups only get in the mesher's way (sweep 64 / 32 / 16 / 8: 5 700-5 930 scans/s against 5 920-5 930, round 6).  Deep octrees (velodyne.yaml: every
     // touched root is on the list and most are split here): 32 -- the launch was 252 wavefronts working through 960 roots, 0.124 -> 0.094 ms per scan.
-    static const int list_div_env = [] { const char* e = getenv("IMMESH_LIST_DIV"); const int v = e ? atoi(e) : 0; return v >= 4 ? v : 0; }();   // (measurement knob, tools/r06_c4div.sh)
-    const int list_div = list_div_env ? list_div_env : (m.split_general ? 32 : 128);
+    const int list_div = list_div_knob ? list_div_knob : (m.split_general ? 32 : 128);   // (Knobs::fused_wgs / list_div: the caller's context)
     const int nb_list = std::min(std::max((n + list_div - 1) / list_div, 32), 4096);
     KLAUNCH(replay_list_kernel, dim3(nb_list), dim3(256), 0, s, m, pt_next, sort_key, pt_data, stats, big_idx, big_order, dbg, (const uint32_t*)general_list,
             (const int32_t*)(m.counters + 10));

@@ -76,3 +76,14 @@ def test_shard_owner_partitions_bricks():
                     assert sorted(D.owners_of_root_voxels(k, 3, world, 0).tolist()) == list(range(world))
                     step = np.zeros(3, np.int64); step[axis] = 8
                     assert (D.owners_of_root_voxels(keys, 3, world, 0) != D.owners_of_root_voxels(keys + step, 3, world, 0)).all()
+    # worlds divisible by 3 or 5: 3 / 5 are no units mod such a world, the colouring would drop an axis -- brick_owner uses the hash whatever the scheme says.
+    # immesh_shard_owner calls brick_owner itself, so it says what the kernels and dist.py say, and scheme 0 equals scheme 1 there: that is the rule
+    for world in (3, 5, 6, 10, 12):
+        keys = rng.integers(-3000, 3000, size=(1500, 3))
+        per_scheme = []
+        for scheme in (0, 1):
+            cfg = capi.avia_config(shard_rank=0, shard_world=world, shard_brick_log2=3, shard_scheme=scheme)
+            lib_owner = np.array([capi.shard_owner(lib, cfg, k) for k in keys])
+            np.testing.assert_array_equal(D.owners_of_root_voxels(keys, 3, world, scheme), lib_owner)
+            per_scheme.append(lib_owner)
+        np.testing.assert_array_equal(per_scheme[0], per_scheme[1])
