@@ -149,6 +149,46 @@ def camera_from_state(lib, state, cam=None):
     return cam
 
 
+class Image(C.Structure):
+    """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("rot", C.c_double * 9), ("pos", C.c_double * 3),
+                ("fov_margin", C.c_double), ("inv_exposure", C.c_double), ("obs_time", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double),
+                ("max_pe_error", C.c_double)]
+
+
+class ColourStats(C.Structure):
+    """immesh_colour_stats"""
+    _fields_ = [(n, C.c_int64) for n in ("n_set", "n_selected", "n_hit", "n_first", "n_updated", "pe_count")] + [("pe_sum", C.c_double), ("min_dis", C.c_double)]
+
+
+COLOUR_STATE_DTYPE = np.dtype([("rgb", "<f8", 3), ("cov", "<f8", 3), ("first_exposure", "<f8"), ("obs_dis", "<f8"), ("last_obs_time", "<f8"),
+                               ("n_obs", "<i4"), ("pad", "<i4")])   # immesh_colour_state
+assert COLOUR_STATE_DTYPE.itemsize == 80 and C.sizeof(ColourStats) == 64 and C.sizeof(Image) == 200
+COLOUR_PLAIN, COLOUR_VIEW = 0, 1
+COLOUR_SET_ALL, COLOUR_SET_IDS, COLOUR_SET_RECENT, COLOUR_SET_RECENT_HEADS = 0, 1, 2, 3
+
+
+def default_image(lib, pixels=None, **over):
+    """immesh_default_image (identity pose, margin 0.005, inverse exposure 0.01, depths 3 / 200, pe 40) around `pixels` ((rows, cols, 3) uint8; the
+    returned structure keeps it alive), fields overridden by keyword"""
+    im = Image()
+    lib.immesh_default_image.argtypes = [C.POINTER(Image)]; lib.immesh_default_image.restype = None
+    lib.immesh_default_image(C.byref(im))
+    if pixels is not None:
+        px = np.asarray(pixels)
+        if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 3 or px.strides[2] != 1 or px.strides[1] != 3:
+            px = np.ascontiguousarray(px, dtype=np.uint8).reshape(px.shape[0], px.shape[1], 3)
+        im._pixels = px
+        im.data = px.ctypes.data; im.rows, im.cols = px.shape[:2]; im.row_stride_bytes = px.strides[0]
+    for k, v in over.items():
+        if k in ("rot", "pos"):
+            getattr(im, k)[:] = [float(x) for x in np.asarray(v, float).reshape(-1)]
+        else:
+            setattr(im, k, v)
+    return im
+
+
 class RegionInfo(C.Structure):
     """immesh_region_info (include/immesh_regions.h): one region bucket of the renderer"""
     _fields_ = [("key", C.c_int32 * 3), ("index", C.c_int32), ("n_triangles", C.c_int32), ("dirty", C.c_int32), ("first", C.c_int64)]
@@ -290,6 +330,10 @@ class HotPath:
         self.ctx = C.c_void_p(self.ctx)
 
     def close(self):
+        if getattr(self, "_colourer", None):                 # the colourer goes before its context
+            g = self.lib.immesh_colourer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
+            g(self._colourer)
+            self._colourer = None
         if getattr(self, "_renderer", None):                 # the renderer goes before its context
             g = self.lib.immesh_renderer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
             g(self._renderer)
@@ -537,6 +581,60 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.renderer(), ms), "renderer_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- vertex colours from camera images (include/immesh_colour.h) ----------------------------------------------------------------------------
+    def colourer(self):
+        """the context's colourer (created at first use, destroyed by close())"""
+        if getattr(self, "_colourer", None) is None:
+            f = self.lib.immesh_colourer_create; f.argtypes = [C.c_void_p]; f.restype = C.c_void_p
+            r = f(self.ctx)
+            if not r:
+                self._check(-1, "colourer_create")
+            self._colourer = C.c_void_p(r)
+        return self._colourer
+
+    def default_image(self, pixels=None, **over):
+        return default_image(self.lib, pixels, **over)
+
+    def colour_image(self, im, model=COLOUR_PLAIN, set=COLOUR_SET_ALL, ids=None, select_min_dis=0.0):
+        """immesh_colour_image: one camera frame onto the vertex colours -> the call's statistics as a dict"""
+        f = self.lib.immesh_colour_image
+        f.argtypes = [C.c_void_p, C.POINTER(Image), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.POINTER(ColourStats)]; f.restype = C.c_int
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        st = ColourStats()
+        self._check(f(self.colourer(), C.byref(im), model, set, _ptr(ids), 0 if ids is None else len(ids), select_min_dis, C.byref(st)), "colour_image")
+        return {n: getattr(st, n) for n, _ in ColourStats._fields_}
+
+    def colour_selected(self):
+        """the render set of the last colour_image -> (ids (n,) int32 ascending, raw uv (n, 2) float32)"""
+        f = self.lib.immesh_colour_selected; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.colourer(), None, None, 0, C.byref(n)), "colour_selected")
+        ids, uv = np.zeros(n.value, np.int32), np.zeros((n.value, 2), np.float32)
+        self._check(f(self.colourer(), _ptr(ids), _ptr(uv), n.value, C.byref(n)), "colour_selected")
+        return ids, uv
+
+    def colour_fetch(self, ids=None, n=None):
+        """immesh_colour_fetch: ids, or (None) the first n vertices (default: every vertex of the map) -> (rgb (n, 3) uint8, states COLOUR_STATE_DTYPE)"""
+        f = self.lib.immesh_colour_fetch; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int32); n = len(ids)
+        elif n is None:
+            n = self.counters()["n_vertices"]
+        rgb, st = np.zeros((n, 3), np.uint8), np.zeros(n, COLOUR_STATE_DTYPE)
+        self._check(f(self.colourer(), _ptr(ids), n, _ptr(rgb), _ptr(st)), "colour_fetch")
+        return rgb, st
+
+    def save_ply_rgb(self, path, smooth_factor=1.0, knn=20, min_views=0, bgr=True):
+        f = self.lib.immesh_save_ply_rgb; f.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_int32, C.c_int32, C.c_int32]; f.restype = C.c_int
+        self._check(f(self.colourer(), path.encode(), smooth_factor, knn, min_views, 1 if bgr else 0), "save_ply_rgb")
+
+    def colour_timing(self):
+        """device milliseconds of the last colour_image: (upload, select, update)"""
+        f = self.lib.immesh_colourer_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.colourer(), ms), "colourer_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def process_scan_strided(self, down_bytes, n_ds, down_stride, raw_bytes, n_raw, raw_stride, raw_int_off, state_prior, state, frame_idx=0, do_mesh=True):
         """immesh_process_scan_strided: down_bytes / raw_bytes = numpy arrays (any dtype) or device pointers holding the pcl-shaped clouds"""
