@@ -189,6 +189,29 @@ def default_image(lib, pixels=None, **over):
     return im
 
 
+class Shade(C.Structure):
+    """immesh_shade (include/immesh_shade.h): the colour pass behind a render"""
+    _fields_ = [("source", C.c_int32), ("axis", C.c_int32), ("light", C.c_int32), ("bgr", C.c_int32), ("min_views", C.c_int32),
+                ("background", C.c_uint8 * 3), ("pad", C.c_uint8), ("axis_min", C.c_double), ("axis_max", C.c_double)]
+
+
+assert C.sizeof(Shade) == 40
+SHADE_WHITE, SHADE_AXIS, SHADE_VERTEX = 0, 1, 2
+
+
+def default_shade(lib, **over):
+    """immesh_default_shade (WHITE, axis 2, light on, black background, range 0 / 0 = from the vertices) with fields overridden by keyword"""
+    sh = Shade()
+    lib.immesh_default_shade.argtypes = [C.POINTER(Shade)]; lib.immesh_default_shade.restype = None
+    lib.immesh_default_shade(C.byref(sh))
+    for k, v in over.items():
+        if k == "background":
+            sh.background[:] = [int(x) for x in v]
+        else:
+            setattr(sh, k, v)
+    return sh
+
+
 class RegionInfo(C.Structure):
     """immesh_region_info (include/immesh_regions.h): one region bucket of the renderer"""
     _fields_ = [("key", C.c_int32 * 3), ("index", C.c_int32), ("n_triangles", C.c_int32), ("dirty", C.c_int32), ("first", C.c_int64)]
@@ -581,6 +604,59 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.renderer(), ms), "renderer_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
+    def default_shade(self, **over):
+        return default_shade(self.lib, **over)
+
+    def _shade_outputs(self, cam, want_rgb, want_depth, want_face):
+        shape = (max(cam.height, 0), max(cam.width, 0))               # (a bad size is the library's to reject)
+        return (np.empty(shape + (3,), np.uint8) if want_rgb else None, np.empty(shape, np.float32) if want_depth else None,
+                np.empty(shape, np.int32) if want_face else None)
+
+    def shade_triangles(self, cam, vtx_xyz, faces, shade, vtx_rgb=None, want_rgb=True, want_depth=True, want_face=True):
+        """immesh_shade_triangles on a host triangle soup -> (rgb (h, w, 3) uint8, depth (h, w) float32, face (h, w) int32), None where not wanted"""
+        f = self.lib.immesh_shade_triangles
+        f.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Shade), C.c_void_p, C.c_void_p,
+                      C.c_void_p]
+        f.restype = C.c_int
+        vtx = np.ascontiguousarray(vtx_xyz, dtype=np.float32).reshape(-1, 3)
+        fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        col = None if vtx_rgb is None else np.ascontiguousarray(vtx_rgb, dtype=np.uint8).reshape(-1, 3)
+        if col is not None and len(col) != len(vtx):
+            raise ValueError("vtx_rgb must hold one byte triple per vertex")
+        rgb, depth, face = self._shade_outputs(cam, want_rgb, want_depth, want_face)
+        self._check(f(self.renderer(), C.byref(cam), _ptr(vtx), len(vtx), _ptr(fc), len(fc), _ptr(col), C.byref(shade), _ptr(rgb), _ptr(depth), _ptr(face)),
+                    "shade_triangles")
+        return rgb, depth, face
+
+    def shade_mesh(self, cam, shade, smooth_factor=1.0, knn=20, colourer=True, want_rgb=True, want_depth=True, want_face=True):
+        """immesh_shade_mesh: the live mesh as mesh_export(smooth_factor, knn) exports it -> (rgb, depth, face).  colourer: True = the context's own
+        (created at first use) when the source is VERTEX, None / False = none, or a raw immesh_colourer pointer"""
+        f = self.lib.immesh_shade_mesh
+        f.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_double, C.c_int32, C.POINTER(Shade), C.c_void_p, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        if colourer is True:
+            colourer = self.colourer() if shade.source == SHADE_VERTEX else None
+        elif colourer is False:
+            colourer = None
+        rgb, depth, face = self._shade_outputs(cam, want_rgb, want_depth, want_face)
+        self._check(f(self.renderer(), C.byref(cam), colourer, smooth_factor, knn, C.byref(shade), _ptr(rgb), _ptr(depth), _ptr(face)), "shade_mesh")
+        return rgb, depth, face
+
+    def shade_range(self):
+        """the AXIS range (lo, hi) the last shade call used; (0, 0) when its source was not AXIS"""
+        f = self.lib.immesh_shade_range; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        lo_hi = (C.c_double * 2)()
+        self._check(f(self.renderer(), lo_hi), "shade_range")
+        return float(lo_hi[0]), float(lo_hi[1])
+
+    def shade_timing(self):
+        """device milliseconds of the last shade call's colour pass alone (render_timing has the same call's rasterize and reinforce)"""
+        f = self.lib.immesh_renderer_last_shade_ms; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = C.c_float(0.0)
+        self._check(f(self.renderer(), C.byref(ms)), "renderer_last_shade_ms")
+        return float(ms.value)
 
     # -- vertex colours from camera images (include/immesh_colour.h) ----------------------------------------------------------------------------
     def colourer(self):

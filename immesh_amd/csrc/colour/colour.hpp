@@ -30,6 +30,13 @@ struct ClCounters {
     unsigned long long pad;
 };
 
+// a colourer's context and its state where it lies in device memory (colour_host.cpp), for the renderer's colour pass (include/immesh_shade.h): every
+// colourer call returns with its stream synchronised, so between two calls the arrays are complete
+struct immesh_colourer;
+struct immesh_ctx;
+immesh_ctx* cl_colourer_ctx(const immesh_colourer* c);
+const ClState& cl_colourer_state(const immesh_colourer* c);
+
 void cl_launch_state_init(hipStream_t s, const ClState& st);
 // counters <- {n_cand, n_sel, 0 ..., key(3e8)}
 void cl_launch_counters_init(hipStream_t s, ClCounters* cnt, int32_t n_cand, int32_t n_sel);

@@ -91,6 +91,9 @@ int cl_check_image(immesh_ctx* c, const immesh_image* im, int32_t model, int32_t
 
 }  // namespace
 
+immesh_ctx* cl_colourer_ctx(const immesh_colourer* c) { return c->ctx; }
+const ClState& cl_colourer_state(const immesh_colourer* c) { return c->st; }
+
 extern "C" {
 
 void immesh_default_image(immesh_image* img) {

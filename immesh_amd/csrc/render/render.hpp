@@ -40,3 +40,27 @@ void rd_launch_hash_insert(hipStream_t s, int64_t n_pix, const float* depth, con
 void rd_launch_hash_keep(hipStream_t s, int64_t n_pix, const float* depth, const uint32_t* tab_min, const uint32_t* slot_of, int32_t* keep);
 // out[koff[i]] = pts[i] for kept pixels; n_out[0] = kept count
 void rd_launch_compact(hipStream_t s, int64_t n_pix, const float* pts, const int32_t* keep, const int32_t* koff, float* out, int64_t* n_out);
+
+// ---- the colour pass behind the rasterizer (include/immesh_shade.h; shade_kernels.hip)
+struct RdShade {                     // the pass as the kernels read it
+    int32_t source, axis, light, bgr, min_views;
+    int32_t range_from_vertices;     // AXIS: lo / hi are decoded from the range keys instead of taken from here
+    float lo, hi;
+    uint32_t background;             // R | G << 8 | B << 16
+};
+// the colourer's state arrays as the vertex-colour kernel reads them (colour/colour.hpp's ClState, without its header)
+struct RdColourState {
+    const double* rgb[3];
+    const double* first_exposure;
+    const int32_t* n_obs;
+};
+// keys[0], keys[1] = order-preserving keys of the smallest and the largest coordinate `axis` over the vertices with three finite coordinates
+// (0xFFFFFFFF / 0 when there is none), in two stages through part (2 * RD_SHADE_RANGE_PARTS words)
+constexpr int RD_SHADE_RANGE_PARTS = 1024;
+void rd_launch_shade_range(hipStream_t s, const float* vtx, int64_t n_vtx, int axis, uint32_t* part, uint32_t* keys);
+// col[i] = R | G << 8 | B << 16 of vertex i (AXIS: Heat; VERTEX: bytes n_vtx x 3, or st when bytes is nullptr); range[0..1] = lo, hi as used
+void rd_launch_shade_colours(hipStream_t s, const RdShade& sh, const float* vtx, int64_t n_vtx, const uint8_t* bytes, const RdColourState& st,
+                             const uint32_t* keys, uint32_t* col, float* range);
+// one lane per pixel in the resolve kernel's tiles: rgb[3 i] from face[i], rec[face], the face's indices and their colours (col: nullptr for WHITE)
+void rd_launch_shade(hipStream_t s, const RdCam& cam, const RdShade& sh, const RdFace* rec, const int32_t* faces, const int32_t* face, const uint32_t* col,
+                     uint8_t* rgb);

@@ -5,6 +5,8 @@
 #include <cstring>
 #include <string>
 #include "../host_ctx.hpp"
+#include "../../../include/immesh_shade.h"
+#include "../colour/colour.hpp"
 #include "render.hpp"
 
 struct RdBuf {   // grow-only device buffer
@@ -16,10 +18,22 @@ struct immesh_renderer {
     immesh_ctx* ctx = nullptr;
     hipStream_t s = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    int64_t* h_small = nullptr;   // pinned: [0] pairs of the render, [1] reinforced points
+    hipEvent_t ev_shade[2] = {nullptr, nullptr};
+    int64_t* h_small = nullptr;   // pinned: [0] pairs of the render, [1] reinforced points, [2] the colour pass's range (two floats)
     RdBuf vtx, faces, rec, cnt, foff, temp, tiles, bins, depth, face, pts, cells, keep, koff, slot, tab, out, small;
+    RdBuf vrgb, vcol, rgb, srange;   // the colour pass: a soup's vertex bytes, packed vertex colours, the image, range keys + range + partials
     int64_t n_points = 0;
     float ms[2] = {0.0f, 0.0f};
+    float shade_ms = 0.0f;
+    double shade_lo_hi[2] = {0.0, 0.0};
+};
+
+// one colour pass behind a render: the checked immesh_shade and where the VERTEX colours come from
+struct RdShadeJob {
+    RdShade sh;
+    const uint8_t* d_bytes = nullptr;   // VERTEX, soup: n_vtx x 3 bytes in device memory
+    RdColourState st = {};              // VERTEX, live mesh: the colourer's arrays
+    uint8_t* rgb_out = nullptr;
 };
 
 namespace {
@@ -58,9 +72,57 @@ int rd_check_camera(immesh_renderer* r, const immesh_camera* cam) {
     return 0;
 }
 
+int rd_check_soup(immesh_renderer* r, const char* who, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
+    immesh_ctx* c = r->ctx;
+    if (n_vtx < 0 || n_faces < 0 || n_faces >= (int64_t)INT_MAX || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
+        c->err = std::string(who) + ": bad vertex / face arrays";
+        return IMMESH_E_INVAL;
+    }
+    for (int64_t i = 0; i < 3 * n_faces; i++)
+        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
+            c->err = std::string(who) + ": face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
+                     std::to_string(n_vtx) + ")";
+            return IMMESH_E_INVAL;
+        }
+    return 0;
+}
+
+int rd_upload_soup(immesh_renderer* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
+    immesh_ctx* c = r->ctx;
+    int rc;
+    if ((rc = rd_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
+    if ((rc = rd_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
+    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
+    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
+    return 0;
+}
+
+// the colour pass's arguments (include/immesh_shade.h) -> job->sh
+int rd_check_shade(immesh_renderer* r, const immesh_shade* sh, RdShadeJob* job) {
+    immesh_ctx* c = r->ctx;
+    if (!sh) { c->err = "shade: immesh_shade is NULL"; return IMMESH_E_INVAL; }
+    if (sh->source != IMMESH_SHADE_WHITE && sh->source != IMMESH_SHADE_AXIS && sh->source != IMMESH_SHADE_VERTEX) {
+        c->err = "shade: unknown source " + std::to_string(sh->source);
+        return IMMESH_E_INVAL;
+    }
+    if (sh->axis < 0 || sh->axis > 2) { c->err = "shade: axis must be 0, 1 or 2 (got " + std::to_string(sh->axis) + ")"; return IMMESH_E_INVAL; }
+    const float lo = (float)sh->axis_min, hi = (float)sh->axis_max;
+    if (!std::isfinite(sh->axis_min) || !std::isfinite(sh->axis_max) || !std::isfinite(lo) || !std::isfinite(hi)) {
+        c->err = "shade: the axis range must be finite (as floats)";
+        return IMMESH_E_INVAL;
+    }
+    RdShade& o = job->sh;
+    o.source = sh->source; o.axis = sh->axis; o.light = sh->light ? 1 : 0; o.bgr = sh->bgr ? 1 : 0; o.min_views = sh->min_views;
+    o.range_from_vertices = sh->axis_min >= sh->axis_max ? 1 : 0;
+    o.lo = lo; o.hi = hi;
+    o.background = (uint32_t)sh->background[0] | ((uint32_t)sh->background[1] << 8) | ((uint32_t)sh->background[2] << 16);
+    return 0;
+}
+
 // rasterize n_faces faces of device arrays (vtx n_vtx x 3 floats, faces n_faces x 3 ints), reinforce, copy the requested outputs to the host
+// with a job: the colour pass behind it (include/immesh_shade.h), on the same stream, under an event pair of its own
 int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, int64_t n_vtx, const int32_t* d_faces, int64_t n_faces, float* depth_out,
-              int32_t* face_out) {
+              int32_t* face_out, const RdShadeJob* job = nullptr) {
     immesh_ctx* c = r->ctx;
     hipStream_t s = r->s;
     r->n_points = 0;
@@ -86,6 +148,11 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
     if ((rc_ = rd_grow(r, r->koff, (size_t)n_pix * 4))) return rc_;
     if ((rc_ = rd_grow(r, r->out, (size_t)n_pix * 12))) return rc_;
     if ((rc_ = rd_grow(r, r->small, 16))) return rc_;
+    if (job) {
+        if ((rc_ = rd_grow(r, r->rgb, (size_t)n_pix * 3))) return rc_;
+        if ((rc_ = rd_grow(r, r->srange, 16 + 8 * (size_t)RD_SHADE_RANGE_PARTS))) return rc_;
+        if (job->sh.source != IMMESH_SHADE_WHITE && (rc_ = rd_grow(r, r->vcol, (size_t)n_vtx * 4))) return rc_;
+    }
     uint32_t mask = 0;
     if (res > 0.0f) {
         uint64_t cap = 1024;
@@ -142,6 +209,27 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
     r->n_points = r->h_small[1];
     (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);
     (void)hipEventElapsedTime(&r->ms[1], r->ev[1], r->ev[2]);
+
+    // ---- colour pass
+    if (job) {
+        const RdShade& sh = job->sh;
+        uint32_t* keys = (uint32_t*)r->srange.p;
+        float* range = (float*)(keys + 2);
+        const bool axis = sh.source == IMMESH_SHADE_AXIS;
+        HIPCHK(c, hipEventRecord(r->ev_shade[0], s));
+        if (axis && sh.range_from_vertices) rd_launch_shade_range(s, d_vtx, n_vtx, sh.axis, (uint32_t*)(range + 2), keys);
+        if (sh.source != IMMESH_SHADE_WHITE) rd_launch_shade_colours(s, sh, d_vtx, n_vtx, job->d_bytes, job->st, keys, (uint32_t*)r->vcol.p, range);
+        rd_launch_shade(s, rc, sh, rec, d_faces, face, sh.source == IMMESH_SHADE_WHITE ? nullptr : (const uint32_t*)r->vcol.p, (uint8_t*)r->rgb.p);
+        HIPCHK(c, hipEventRecord(r->ev_shade[1], s));
+        if (axis) HIPCHK(c, hipMemcpyAsync(r->h_small + 2, range, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&r->shade_ms, r->ev_shade[0], r->ev_shade[1]);
+        float lo_hi[2] = {0.0f, 0.0f};
+        if (axis) std::memcpy(lo_hi, r->h_small + 2, 8);
+        r->shade_lo_hi[0] = (double)lo_hi[0]; r->shade_lo_hi[1] = (double)lo_hi[1];
+        if (job->rgb_out) HIPCHK(c, hipMemcpy(job->rgb_out, r->rgb.p, (size_t)n_pix * 3, hipMemcpyDeviceToHost));
+    }
     if (depth_out) HIPCHK(c, hipMemcpy(depth_out, depth, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
     if (face_out) HIPCHK(c, hipMemcpy(face_out, face, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
     return 0;
@@ -177,7 +265,8 @@ immesh_renderer* immesh_renderer_create(immesh_ctx* ctx) {
     r->ctx = ctx;
     bool ok = hipStreamCreateWithFlags(&r->s, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; i < 3 && ok; i++) ok = hipEventCreate(&r->ev[i]) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&r->h_small, 16) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreate(&r->ev_shade[i]) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&r->h_small, 32) == hipSuccess;
     if (!ok) {
         ctx->err = "immesh_renderer_create: stream / event / pinned allocation failed";
         immesh_renderer_destroy(r);
@@ -191,9 +280,11 @@ void immesh_renderer_destroy(immesh_renderer* r) {
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
     for (RdBuf* b : {&r->vtx, &r->faces, &r->rec, &r->cnt, &r->foff, &r->temp, &r->tiles, &r->bins, &r->depth, &r->face, &r->pts, &r->cells, &r->keep,
-                     &r->koff, &r->slot, &r->tab, &r->out, &r->small})
+                     &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->vrgb, &r->vcol, &r->rgb, &r->srange})
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t e : r->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->ev_shade)
         if (e) (void)hipEventDestroy(e);
     if (r->h_small) (void)hipHostFree(r->h_small);
     if (r->s) (void)hipStreamDestroy(r->s);
@@ -206,21 +297,9 @@ int immesh_render_triangles(immesh_renderer* r, const immesh_camera* cam, const 
     immesh_ctx* c = r->ctx;
     int rc = rd_check_camera(r, cam);
     if (rc) return rc;
-    if (n_vtx < 0 || n_faces < 0 || n_faces >= (int64_t)INT_MAX || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
-        c->err = "render_triangles: bad vertex / face arrays";
-        return IMMESH_E_INVAL;
-    }
-    for (int64_t i = 0; i < 3 * n_faces; i++)
-        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
-            c->err = "render_triangles: face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
-                     std::to_string(n_vtx) + ")";
-            return IMMESH_E_INVAL;
-        }
+    if ((rc = rd_check_soup(r, "render_triangles", vtx_xyz, n_vtx, faces, n_faces))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if ((rc = rd_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
-    if ((rc = rd_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
-    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
-    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
+    if ((rc = rd_upload_soup(r, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     return rd_render(r, cam, (const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p, n_faces, depth_out, face_out);
 }
 
@@ -253,6 +332,76 @@ int immesh_render_points(immesh_renderer* r, float* xyz_out, int64_t cap, int64_
 int immesh_renderer_last_timing(immesh_renderer* r, float ms[2]) {
     if (!r || !ms) return IMMESH_E_INVAL;
     ms[0] = r->ms[0]; ms[1] = r->ms[1];
+    return 0;
+}
+
+// ---- include/immesh_shade.h
+void immesh_default_shade(immesh_shade* sh) {
+    if (!sh) return;
+    std::memset(sh, 0, sizeof(*sh));
+    sh->source = IMMESH_SHADE_WHITE;
+    sh->axis = 2;
+    sh->light = 1;
+}
+
+int immesh_shade_triangles(immesh_renderer* r, const immesh_camera* cam, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces,
+                           const uint8_t* vtx_rgb, const immesh_shade* sh, uint8_t* rgb_out, float* depth_out, int32_t* face_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    int rc = rd_check_camera(r, cam);
+    if (rc) return rc;
+    RdShadeJob job;
+    if ((rc = rd_check_shade(r, sh, &job))) return rc;
+    if ((rc = rd_check_soup(r, "shade_triangles", vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    const bool bytes = sh->source == IMMESH_SHADE_VERTEX;
+    if (bytes && !vtx_rgb) { c->err = "shade_triangles: source VERTEX without vertex colours"; return IMMESH_E_INVAL; }
+    (void)hipSetDevice(c->cfg.device);
+    if ((rc = rd_upload_soup(r, vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    if (bytes) {
+        if ((rc = rd_grow(r, r->vrgb, (size_t)n_vtx * 3))) return rc;
+        if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vrgb.p, vtx_rgb, (size_t)n_vtx * 3, hipMemcpyHostToDevice, r->s));
+        job.d_bytes = (const uint8_t*)r->vrgb.p;
+    }
+    job.rgb_out = rgb_out;
+    return rd_render(r, cam, (const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p, n_faces, depth_out, face_out, &job);
+}
+
+int immesh_shade_mesh(immesh_renderer* r, const immesh_camera* cam, immesh_colourer* colourer, double smooth_factor, int32_t knn, const immesh_shade* sh,
+                      uint8_t* rgb_out, float* depth_out, int32_t* face_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    if (c->mesh.shard_world > 1) { c->err = "shade_mesh: not available on a sharded mesher (shard_mesh)"; return IMMESH_E_INVAL; }
+    int rc = rd_check_camera(r, cam);
+    if (rc) return rc;
+    RdShadeJob job;
+    if ((rc = rd_check_shade(r, sh, &job))) return rc;
+    const bool vertex = sh->source == IMMESH_SHADE_VERTEX;
+    if (vertex && !colourer) { c->err = "shade_mesh: source VERTEX without a colourer"; return IMMESH_E_INVAL; }
+    if (vertex && cl_colourer_ctx(colourer) != c) { c->err = "shade_mesh: the colourer belongs to another context"; return IMMESH_E_INVAL; }
+    int64_t nv = 0, nf = 0;
+    if ((rc = immesh_mesh_export(c, smooth_factor, knn, &nv, &nf))) return rc;   // synchronises the ctx stream: the arrays are complete
+    if (nf >= (int64_t)INT_MAX) { c->err = "shade_mesh: more than 2^31 - 2 faces"; return IMMESH_E_CAPACITY; }
+    if (vertex) {
+        const ClState& st = cl_colourer_state(colourer);   // export vertex i is vertex i of the map (immesh_save_ply_rgb)
+        if (nv > st.cap) { c->err = "shade_mesh: the export has more vertices than the colourer holds"; return IMMESH_E_CAPACITY; }
+        for (int k = 0; k < 3; k++) job.st.rgb[k] = st.rgb[k];
+        job.st.first_exposure = st.first_exposure; job.st.n_obs = st.n_obs;
+    }
+    job.rgb_out = rgb_out;
+    const MeshHost& h = c->mesh_host;
+    (void)hipSetDevice(c->cfg.device);
+    return rd_render(r, cam, (const float*)h.exp_vtx, nv, h.exp_faces, nf, depth_out, face_out, &job);
+}
+
+int immesh_shade_range(immesh_renderer* r, double lo_hi[2]) {
+    if (!r || !lo_hi) return IMMESH_E_INVAL;
+    lo_hi[0] = r->shade_lo_hi[0]; lo_hi[1] = r->shade_lo_hi[1];
+    return 0;
+}
+
+int immesh_renderer_last_shade_ms(immesh_renderer* r, float* ms) {
+    if (!r || !ms) return IMMESH_E_INVAL;
+    *ms = r->shade_ms;
     return 0;
 }
 

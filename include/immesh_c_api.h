@@ -428,4 +428,5 @@ int immesh_profile_read(immesh_ctx* ctx, immesh_kernel_stat* out, int32_t cap, i
 /* mesh depth images and LiDAR point reinforcement (README 6.1): immesh_render_*, in a header of its own */
 #include "immesh_render.h"
 #include "immesh_colour.h"
+#include "immesh_shade.h"
 #endif
