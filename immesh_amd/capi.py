@@ -225,6 +225,50 @@ class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in COUNTER_FIELDS]
 
 
+# -- checkpoints (include/immesh_checkpoint.h) ------------------------------------------------------------------------------------------------
+E_INVAL, E_CAPACITY, E_IO, E_FORMAT = -1, -4, -6, -7
+CHECKPOINT_VERSION = 1
+CHECKPOINT_COUNT_FIELDS = ("n_root_voxels", "n_nodes", "n_point_chunks", "n_free_chunks", "n_ext_tables", "n_leaf_chunks", "n_vertices", "n_mesh_voxels",
+                           "n_triangles_pool", "n_triangles_live", "n_adj_chunks", "n_regions", "scans_meshed", "map_updates")
+
+
+class CheckpointSection(C.Structure):
+    """immesh_checkpoint_section: one entry of a checkpoint's section table"""
+    _fields_ = [("name", C.c_char * 24), ("offset", C.c_int64), ("bytes", C.c_int64), ("records", C.c_int64), ("checksum", C.c_uint64)]
+
+
+class CheckpointInfo(C.Structure):
+    """immesh_checkpoint_info"""
+    _fields_ = ([("version", C.c_int32), ("n_sections", C.c_int32), ("has_regions", C.c_int32), ("has_colour", C.c_int32), ("file_bytes", C.c_int64), ("cfg", Config)] +
+                [(n, C.c_int64) for n in CHECKPOINT_COUNT_FIELDS] + [("ms", C.c_float * 4)])
+
+
+class CheckpointError(RuntimeError):
+    """a refused checkpoint call: .rc is the IMMESH_E_* code, the text names the fault"""
+    def __init__(self, what, rc, msg):
+        super().__init__(f"{what} failed rc={rc}: {msg}")
+        self.rc, self.msg = rc, msg
+
+
+def _checkpoint_info_dict(info):
+    out = {n: getattr(info, n) for n in ("version", "n_sections", "has_regions", "has_colour", "file_bytes") + CHECKPOINT_COUNT_FIELDS}
+    out["cfg"] = info.cfg
+    out["ms"] = tuple(float(v) for v in info.ms)
+    return out
+
+
+def checkpoint_probe(lib, path, cap=256):
+    """immesh_checkpoint_probe (host only, needs no context) -> (info dict, [section dicts]); CheckpointError when the file is refused"""
+    f = lib.immesh_checkpoint_probe
+    f.argtypes = [C.c_char_p, C.POINTER(CheckpointInfo), C.POINTER(CheckpointSection), C.c_int32, C.c_char_p, C.c_int32]; f.restype = C.c_int
+    info, secs, err = CheckpointInfo(), (CheckpointSection * cap)(), C.create_string_buffer(512)
+    rc = f(os.fsencode(path), C.byref(info), secs, cap, err, len(err))
+    if rc != 0:
+        raise CheckpointError("immesh_checkpoint_probe", rc, err.value.decode())
+    out = [{"name": s.name.decode(), "offset": s.offset, "bytes": s.bytes, "records": s.records, "checksum": s.checksum} for s in secs[:min(cap, info.n_sections)]]
+    return _checkpoint_info_dict(info), out
+
+
 def avia_config(**over):
     """config/avia.yaml + launch/mapping_avia.launch (SURVEY.md section 8 constants table)."""
     c = Config()
@@ -711,6 +755,29 @@ class HotPath:
         ms = (C.c_float * 3)()
         self._check(f(self.colourer(), ms), "colourer_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # -- checkpoints (include/immesh_checkpoint.h) -------------------------------------------------------------------------------------------------
+    def _checkpoint(self, which, path, colourer):
+        f = getattr(self.lib, "immesh_checkpoint_" + which)
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(CheckpointInfo)]; f.restype = C.c_int
+        col = self.colourer() if colourer is True else (getattr(self, "_colourer", None) if colourer is None else (colourer or None))
+        info = CheckpointInfo()
+        rc = f(self.ctx, col, os.fsencode(path), C.byref(info))
+        if rc != 0:
+            g = self.lib.immesh_last_error; g.restype = C.c_char_p; g.argtypes = [C.c_void_p]
+            raise CheckpointError("immesh_checkpoint_" + which, rc, g(self.ctx).decode())
+        return _checkpoint_info_dict(info)
+
+    def checkpoint_save(self, path, colourer=None):
+        """immesh_checkpoint_save -> info dict.  colourer: None = the context's colourer if one was created, True = create one, False = without colours"""
+        return self._checkpoint("save", path, colourer)
+
+    def checkpoint_load(self, path, colourer=None):
+        """immesh_checkpoint_load into this (unused) context -> info dict; colourer as for checkpoint_save"""
+        return self._checkpoint("load", path, colourer)
+
+    def checkpoint_probe(self, path):
+        return checkpoint_probe(self.lib, path)
 
     def process_scan_strided(self, down_bytes, n_ds, down_stride, raw_bytes, n_raw, raw_stride, raw_int_off, state_prior, state, frame_idx=0, do_mesh=True):
         """immesh_process_scan_strided: down_bytes / raw_bytes = numpy arrays (any dtype) or device pointers holding the pcl-shaped clouds"""
