@@ -487,6 +487,18 @@ class HotPath:
         self._check(f(self.ctx, _ptr(out), len(out), C.byref(n)), "mesh_neighbourhood_sizes")
         return out[:n.value]
 
+    def mesh_old_set_sizes(self):
+        """per voxel of the last meshed scan, in the order of mesh_neighbourhood_sizes: the live triangles whose smallest vertex lies in the
+        neighbourhood, i.e. what the device gathers from its smallest-vertex lists before the containment filter (oracle only: test introspection)."""
+        if self.prefix != "orc_":
+            raise RuntimeError("mesh_old_set_sizes is an introspection entry of the oracle; the product library has no such entry point")
+        f = self._f("mesh_old_set_sizes"); f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]; f.restype = C.c_int
+        n = C.c_int32(0)
+        self._check(f(self.ctx, None, 0, C.byref(n)), "mesh_old_set_sizes")
+        out = np.zeros(max(1, n.value), np.int32)
+        self._check(f(self.ctx, _ptr(out), len(out), C.byref(n)), "mesh_old_set_sizes")
+        return out[:n.value]
+
     def mesh_world_scan(self):
         """the world-frame scan (n x 4 float32) the newest finished mesh job was handed (parity diagnostics)"""
         f = self._f("mesh_world_scan"); f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]; f.restype = C.c_int

@@ -198,7 +198,7 @@ IMD int df_triangulate(const int n, const int lane, const int li, const double s
             // and the set need not be a disk: the general path then takes the connected part around the triangle that contains p, as the checker does
             // (oracle/orc_delaunay.hpp header).  Never on points in general position (0 of 300 000 insertions of the bench's stream, CPU count).
             if (X - ndies != 2) { bail = true; break; }
-            if (X > DF_XCAP) { bail = true; break; }
+            if (X > DF_XCAP) { bail = true; break; }   // (cannot hold at n <= 64: a cavity's boundary has at most n + 1 = 65 vertices, hence edges)
             if (X > 0) {
 #pragma unroll
                 for (int j = 0; j < K; j++)
@@ -211,7 +211,7 @@ IMD int df_triangulate(const int n, const int lane, const int li, const double s
                 // a slot is either a freed one (rank among the freed slots, in slot order) or a new one at the high-water mark -- never both
                 const int F0 = __popcll(freem[0]), F1 = hi ? __popcll(freem[K - 1]) : 0, F = F0 + F1;
                 const int extra = X > F ? X - F : 0;
-                if (nt + extra > 64 * K) { bail = true; break; }
+                if (nt + extra > 64 * K) { bail = true; break; }   // (cannot hold at n <= 64: the slot table peaks at 2 n - 2 = 126 entries)
 #pragma unroll
                 for (int f = 0; f < K; f++) {
                     if (f > 0 && !hi && nt + extra <= 64) continue;

@@ -356,6 +356,15 @@ int orc_mesh_neighbourhood_sizes(void* p, int32_t* out, int32_t cap, int32_t* n_
     if (out) { if ((int32_t)m.n_u_list.size() > cap) return -4; std::memcpy(out, m.n_u_list.data(), m.n_u_list.size() * 4); }
     return 0;
 }
+// checker only (no immesh_ counterpart): per meshed voxel of the last scan, in the order of orc_mesh_neighbourhood_sizes, the number of live triangles
+// whose smallest vertex is in the voxel's neighbourhood -- the entries a device gathers from its smallest-vertex lists before the containment filter
+int orc_mesh_old_set_sizes(void* p, int32_t* out, int32_t cap, int32_t* n_out) {
+    OrcCtx* o = (OrcCtx*)p;
+    const MeshScanOut& m = o->mout;
+    *n_out = (int32_t)m.old_set_list.size();
+    if (out) { if ((int32_t)m.old_set_list.size() > cap) return -4; std::memcpy(out, m.old_set_list.data(), m.old_set_list.size() * 4); }
+    return 0;
+}
 int orc_mesh_fetch(void* p, float* new_vtx_xyz, int32_t* tri_add, uint8_t* flip_add, int32_t* tri_rem, int32_t* tri_upd, uint8_t* flip_upd,
                    int32_t* smooth_ids, double* smooth_xyz) {
     OrcCtx* o = (OrcCtx*)p;

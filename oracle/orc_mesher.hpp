@@ -43,6 +43,7 @@ struct MeshScanOut {
     std::vector<double> smooth_xyz;
     int v_act = 0;
     std::vector<int> n_u_list;          // neighbourhood size of every triangulated voxel, in voxel order (diagnostics)
+    std::vector<int> old_set_list;      // same order: live triangles whose smallest vertex lies in the neighbourhood, before the containment filter (diagnostics)
 };
 
 struct Mesher {
@@ -260,6 +261,16 @@ struct Mesher {
             const std::vector<int>& tri_ids = w.tri_ids;
             const std::set<long> rel(ids.begin(), ids.end());
             out.n_u_list.push_back((int)ids.size());
+            {   // diagnostics: what a per-smallest-vertex triangle list hands over for this neighbourhood (the commits of a scan come after all its voxels,
+                // so adj is the live set the scan started with); triplets are stored sorted, t[0] is the smallest vertex
+                int n_old = 0;
+                for (int id : ids) {
+                    auto it = adj.find(id);
+                    if (it == adj.end()) continue;
+                    for (const Tri& t : it->second) n_old += t[0] == id;
+                }
+                out.old_set_list.push_back(n_old);
+            }
             if (cnt) { cnt->c20 += w.c20; cnt->n_u += (long)ids.size(); cnt->n_degenerate_skips += w.n_skip; }
             // a21 find_relative_triangulation_combination, triangle.hpp:223-246
             std::set<Tri> old;

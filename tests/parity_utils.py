@@ -1,5 +1,21 @@
-"""Helpers shared by the GPU parity tests: canonical comparison of plane tables (normals up to the joint sign flip)."""
+"""Helpers shared by the GPU parity tests: canonical comparison of plane tables (normals up to the joint sign flip), the per-scan
+comparison of the mesher's result lists."""
 import numpy as np
+
+
+def compare_scan(mo, mh, tag=""):
+    """mo: the oracle's lists of one meshed scan, mh: the HIP library's.  Bar (BASELINE.json north_star): ids and every triangle / flip list bit-equal,
+    smoothed positions within 1e-9 (f64 means of exactly representable values; the sum order is the same on both sides)."""
+    assert mh["vtx_base"] == mo["vtx_base"], tag
+    np.testing.assert_array_equal(mh["new_vtx"], mo["new_vtx"], err_msg=f"{tag} new vertices")
+    assert mh["n_voxels_meshed"] == mo["n_voxels_meshed"], tag
+    np.testing.assert_array_equal(mh["tri_rem"], mo["tri_rem"], err_msg=f"{tag} tri_rem")
+    np.testing.assert_array_equal(mh["tri_add"], mo["tri_add"], err_msg=f"{tag} tri_add")
+    np.testing.assert_array_equal(mh["flip_add"], mo["flip_add"], err_msg=f"{tag} flip_add")
+    np.testing.assert_array_equal(mh["tri_upd"], mo["tri_upd"], err_msg=f"{tag} tri_upd")
+    np.testing.assert_array_equal(mh["flip_upd"], mo["flip_upd"], err_msg=f"{tag} flip_upd")
+    np.testing.assert_array_equal(mh["smooth_ids"], mo["smooth_ids"], err_msg=f"{tag} smooth ids")
+    np.testing.assert_allclose(mh["smooth_xyz"], mo["smooth_xyz"], rtol=0, atol=1e-9, err_msg=f"{tag} smooth xyz")
 
 
 def plane_index(recs):

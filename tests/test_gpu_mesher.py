@@ -6,6 +6,7 @@ import pytest
 
 from immesh_amd import capi, synth
 from conftest import make_oracle, make_hip
+from parity_utils import compare_scan as _compare_scan
 
 pytestmark = pytest.mark.gpu
 
@@ -19,19 +20,6 @@ def _world_scan(k, n, cfg):
     out = raw.copy()
     out[:, :3] = pw.astype(np.float32)
     return np.ascontiguousarray(out), t
-
-
-def _compare_scan(mo, mh, tag=""):
-    assert mh["vtx_base"] == mo["vtx_base"], tag
-    np.testing.assert_array_equal(mh["new_vtx"], mo["new_vtx"], err_msg=f"{tag} new vertices")
-    assert mh["n_voxels_meshed"] == mo["n_voxels_meshed"], tag
-    np.testing.assert_array_equal(mh["tri_rem"], mo["tri_rem"], err_msg=f"{tag} tri_rem")
-    np.testing.assert_array_equal(mh["tri_add"], mo["tri_add"], err_msg=f"{tag} tri_add")
-    np.testing.assert_array_equal(mh["flip_add"], mo["flip_add"], err_msg=f"{tag} flip_add")
-    np.testing.assert_array_equal(mh["tri_upd"], mo["tri_upd"], err_msg=f"{tag} tri_upd")
-    np.testing.assert_array_equal(mh["flip_upd"], mo["flip_upd"], err_msg=f"{tag} flip_upd")
-    np.testing.assert_array_equal(mh["smooth_ids"], mo["smooth_ids"], err_msg=f"{tag} smooth ids")
-    np.testing.assert_allclose(mh["smooth_xyz"], mo["smooth_xyz"], rtol=0, atol=1e-9, err_msg=f"{tag} smooth xyz")
 
 
 @pytest.mark.parametrize("split", ["0", "1"])
@@ -295,7 +283,9 @@ def test_long_async_stream_under_all_arrangements(hip_lib, monkeypatch):
 
 def test_mesh_volumetric_cloud(oracle_lib, hip_lib):
     """A space-filling cloud (vegetation-like): up to ~45 vertices per mesh voxel, thousands of candidates around a voxel (the kNN kernel
-    stages them in several LDS batches), neighbourhoods above 256 vertices (the large-neighbourhood Delaunay instantiation)."""
+    stages them in several LDS batches), neighbourhoods of 65..256 vertices (the oracle's maximum on this input is 165: the general triangulation
+    with its tables in LDS).  Neighbourhoods above 256 -- the instantiation with its tables in global scratch -- need a mesh_voxel / mesh_min_spacing
+    ratio above the shipped 4: tests/test_gpu_mesher_paths.py."""
     cfg = capi.avia_config(cap_root_voxels=1 << 12, cap_scan_points=100000, cap_vertices=1 << 16, cap_triangles=1 << 20, mesh_append_budget=20000)
     o, h = make_oracle(oracle_lib, cfg), make_hip(hip_lib, cfg)
     rng = np.random.default_rng(21)

@@ -13,8 +13,7 @@ import pytest
 
 from immesh_amd import capi, synth
 from conftest import make_oracle, make_hip
-from parity_utils import compare_plane_tables_fast, ComposedRunChecker
-from test_gpu_mesher import _compare_scan
+from parity_utils import compare_plane_tables_fast, ComposedRunChecker, compare_scan as _compare_scan
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 TOL = 1e-5
