@@ -149,6 +149,23 @@ def camera_from_state(lib, state, cam=None):
     return cam
 
 
+class RayFrame(C.Structure):
+    """immesh_ray_frame (include/immesh_raycast.h): sensor-to-world rotation (row-major) and the sensor origin in the world"""
+    _fields_ = [("rot", C.c_double * 9), ("pos", C.c_double * 3)]
+
+
+assert C.sizeof(RayFrame) == 96
+RAY_NEAREST, RAY_ANY = 0, 1
+
+
+def ray_frame(rot=None, pos=None):
+    """a RayFrame from a 3 x 3 rotation and a position (identity / origin by default)"""
+    fr = RayFrame()
+    fr.rot[:] = [float(x) for x in (np.eye(3) if rot is None else np.asarray(rot, float)).reshape(-1)]
+    fr.pos[:] = [float(x) for x in (np.zeros(3) if pos is None else np.asarray(pos, float)).reshape(-1)]
+    return fr
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -401,6 +418,10 @@ class HotPath:
             g = self.lib.immesh_colourer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
             g(self._colourer)
             self._colourer = None
+        if getattr(self, "_raycaster", None):                # the ray caster goes before its context
+            g = self.lib.immesh_raycaster_destroy; g.argtypes = [C.c_void_p]; g.restype = None
+            g(self._raycaster)
+            self._raycaster = None
         if getattr(self, "_renderer", None):                 # the renderer goes before its context
             g = self.lib.immesh_renderer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
             g(self._renderer)
@@ -660,6 +681,77 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.renderer(), ms), "renderer_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- rays cast at the mesh (include/immesh_raycast.h) ---------------------------------------------------------------------------------------
+    def raycaster(self):
+        """the context's ray caster (created at first use, destroyed by close())"""
+        if getattr(self, "_raycaster", None) is None:
+            f = self.lib.immesh_raycaster_create; f.argtypes = [C.c_void_p]; f.restype = C.c_void_p
+            r = f(self.ctx)
+            if not r:
+                self._check(-1, "raycaster_create")
+            self._raycaster = C.c_void_p(r)
+        return self._raycaster
+
+    def ray_frame_from_state(self, state):
+        """immesh_ray_frame_from_state: the LiDAR frame of a pose (make_state layout) under the configuration's extrinsic -> RayFrame"""
+        f = self.lib.immesh_ray_frame_from_state; f.argtypes = [C.POINTER(Config), C.c_void_p, C.POINTER(RayFrame)]; f.restype = C.c_int
+        st = np.ascontiguousarray(state, dtype=np.float64)
+        fr = RayFrame()
+        rc = f(C.byref(self.cfg), _ptr(st), C.byref(fr))
+        if rc != 0:
+            raise RuntimeError(f"immesh_ray_frame_from_state failed rc={rc}")
+        return fr
+
+    def _raycast_sizes(self):
+        f = self.lib.immesh_raycast_sizes; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        nv, nf, ni = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(f(self.raycaster(), C.byref(nv), C.byref(nf), C.byref(ni)), "raycast_sizes")
+        return nv.value, nf.value, ni.value
+
+    def raycast_build_triangles(self, vtx_xyz, faces):
+        """immesh_raycast_build_triangles on a host triangle soup -> (n_vtx, n_faces, faces in the hierarchy)"""
+        f = self.lib.immesh_raycast_build_triangles; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]; f.restype = C.c_int
+        vtx = np.ascontiguousarray(vtx_xyz, dtype=np.float32).reshape(-1, 3)
+        fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        self._check(f(self.raycaster(), _ptr(vtx), len(vtx), _ptr(fc), len(fc)), "raycast_build_triangles")
+        return self._raycast_sizes()
+
+    def raycast_build_mesh(self, smooth_factor=1.0, knn=20):
+        """immesh_raycast_build_mesh: a snapshot of the live mesh as mesh_export(smooth_factor, knn) exports it -> (n_vtx, n_faces, faces in the hierarchy)"""
+        f = self.lib.immesh_raycast_build_mesh; f.argtypes = [C.c_void_p, C.c_double, C.c_int32]; f.restype = C.c_int
+        self._check(f(self.raycaster(), smooth_factor, knn), "raycast_build_mesh")
+        return self._raycast_sizes()
+
+    def raycast(self, frame, dirs, origins=None, t_min=0.0, t_max=200.0, mode=RAY_NEAREST, want_t=True, want_face=True):
+        """immesh_raycast: dirs (n, 3) and origins (n, 3) or None, in the sensor frame -> (t (n,) float32 or None, face (n,) int32 or None); -1 = miss"""
+        f = self.lib.immesh_raycast
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        o = None if origins is None else np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        if o is not None and len(o) != len(d):
+            raise ValueError("raycast: origins and dirs differ in length")
+        t = np.empty(len(d), np.float32) if want_t else None
+        face = np.empty(len(d), np.int32) if want_face else None
+        self._check(f(self.raycaster(), C.byref(frame), _ptr(d), _ptr(o), len(d), t_min, t_max, mode, _ptr(t), _ptr(face)), "raycast")
+        return t, face
+
+    def raycast_points(self, downsample_res=0.01):
+        """reinforced points of the last NEAREST cast, ray order -> (n, 3) float32"""
+        f = self.lib.immesh_raycast_points; f.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), downsample_res, None, 0, C.byref(n)), "raycast_points")
+        out = np.zeros((n.value, 3), np.float32)
+        self._check(f(self.raycaster(), downsample_res, _ptr(out), n.value, C.byref(n)), "raycast_points")
+        return out
+
+    def raycast_timing(self):
+        """device milliseconds of the last (build, cast, reinforce)"""
+        f = self.lib.immesh_raycaster_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.raycaster(), ms), "raycaster_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

@@ -1,0 +1,53 @@
+// Ray casting at a triangle soup (include/immesh_raycast.h): the hierarchy's records and the launches raycast_host.cpp sequences.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+constexpr int RC_BLOCK = 256;
+// The sort key of a face is (Morton code of its box centre, position among the faces that enter the tree): RC_CODE_BITS + RC_INDEX_BITS bits, all
+// keys distinct.  Karras' construction gives every interior node a distinct common-prefix length on a root-to-leaf path, so a leaf has at most
+// RC_CODE_BITS + RC_INDEX_BITS interior ancestors.  The traversal pushes at most one entry (the farther child) per interior node on its current
+// path, so its stack never holds more than that many entries, whatever the soup (300 copies of one face, centres at 2^-k).
+constexpr int RC_AXIS_BITS = 21;
+constexpr int RC_CODE_BITS = 3 * RC_AXIS_BITS;
+constexpr int RC_INDEX_BITS = 30;                 // at most 2^30 faces (checked by the host): positions differ in one of their low 30 bits
+constexpr int RC_STACK = 96;
+static_assert(RC_STACK >= RC_CODE_BITS + RC_INDEX_BITS, "the traversal stack must hold one entry per bit of the sort key");
+static_assert(RC_CODE_BITS <= 63, "the code's top bit stays clear: clz of two distinct codes is >= 1");
+
+// one interior node, 64 B: the float boxes of its two children (min / max of float coordinates: they contain their faces' float boxes exactly)
+// and the children themselves -- >= 0: an interior node, < 0: ~child is a face index (a leaf holds one face)
+struct alignas(16) RcNode {
+    float lo[2][3], hi[2][3];
+    int32_t child[2];
+    int32_t parent;                               // (parent node << 1) | side; -1: the root (node 0)
+    int32_t count;                                // refit: children that have arrived
+};
+static_assert(sizeof(RcNode) == 64, "RcNode layout");
+
+struct RcFrame { double rot[9], pos[3]; };
+
+// build -----------------------------------------------------------------------------------------------------------------------------------
+// flag[f] = 1 when face f enters the tree (indices in range, nine finite coordinates)
+void rc_launch_mark(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, int32_t* flag);
+// ids[off[f]] = f for the marked faces, box[6 i] = the float box (lo xyz, hi xyz) of ids[i]; bounds[6] (order-preserving keys, preset to
+// 0xFFFFFFFF x 3, 0 x 3) = min / max over the boxes' centres;  n_in[0] = the number of marked faces
+void rc_launch_compact(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, const int32_t* flag, const int32_t* off, int32_t* ids,
+                       float* box, uint32_t* bounds, int64_t* n_in);
+// code[i] = the Morton code of box i's centre in the bounds, iota[i] = i (the sort's values)
+void rc_launch_codes(hipStream_t s, const float* box, int64_t n_in, const uint32_t* bounds, unsigned long long* code, int32_t* iota);
+// Karras' construction over the sorted codes (ties broken by position): nodes[0 .. n_in - 2], leaf_parent[i] = (node << 1) | side; sorted leaf i is
+// face ids[pos_sorted[i]].  n_in >= 2.
+void rc_launch_hierarchy(hipStream_t s, const unsigned long long* code, const int32_t* ids, const int32_t* pos_sorted, int64_t n_in, RcNode* nodes,
+                         int32_t* leaf_parent);
+// bottom-up refit, one lane per leaf, one counter per interior node
+void rc_launch_refit(hipStream_t s, const float* box, const int32_t* pos_sorted, const int32_t* leaf_parent, int64_t n_in, RcNode* nodes);
+// the tree of a single face: node 0 with that face as both children (a face tested twice gives the same fragment twice)
+void rc_launch_single(hipStream_t s, const float* box, const int32_t* ids, RcNode* nodes);
+
+// cast: t[i], face[i] per the contract (mode 0 NEAREST, 1 ANY); n_in == 0: every ray misses
+void rc_launch_cast(hipStream_t s, const RcFrame& fr, const float* dirs, const float* origins, int64_t n_rays, double t_min, double t_max, int mode,
+                    const float* vtx, const int32_t* faces, const RcNode* nodes, int64_t n_in, float* t, int32_t* face);
+// reinforce: pts[3 i] of the hit rays (t[i] >= 0), cells when res > 0, keep[i] = res > 0 ? 0 : hit
+void rc_launch_points(hipStream_t s, const RcFrame& fr, const float* dirs, const float* origins, int64_t n_rays, float res, const float* t, float* pts,
+                      float* cells, int32_t* keep);

@@ -1,0 +1,317 @@
+// Host side of the ray caster (include/immesh_raycast.h): argument checks, grow-only buffers, the build and cast sequences on the caster's stream.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "../host_ctx.hpp"
+#include "../../../include/immesh_raycast.h"
+#include "../render/render.hpp"
+#include "raycast.hpp"
+
+struct RcBuf {   // grow-only device buffer
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+struct immesh_raycaster {
+    immesh_ctx* ctx = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // build, cast, reinforce: begin / end
+    int64_t* h_small = nullptr;   // pinned: [0] faces in the tree, [1] reinforced points
+    RcBuf vtx, faces, nodes;                                                       // the built snapshot
+    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
+    RcBuf dirs[2], org[2], t[2], face[2];                                          // the last cast of each mode ([0] NEAREST: the reinforce pass reads it)
+    RcBuf pts, cells, keep, koff, slot, tab, out, small;                           // reinforce
+    bool built = false;
+    int64_t n_vtx = 0, n_faces = 0, n_in = 0;
+    // the last NEAREST cast, as the reinforce pass reads it
+    bool have_cast = false, have_origins = false;
+    int64_t n_rays = 0;
+    RcFrame frame = {};
+    int64_t n_points = 0;
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+};
+
+namespace {
+
+constexpr int64_t RC_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;
+
+int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (b.bytes >= bytes) return 0;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.bytes = 0;
+    const size_t want = bytes + bytes / 4;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        r->ctx->err = "raycast: hipMalloc(" + std::to_string(want) + " B) failed";
+        return IMMESH_E_NOMEM;
+    }
+    b.bytes = want;
+    return 0;
+}
+
+int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
+    immesh_ctx* c = r->ctx;
+    if (n_vtx < 0 || n_faces < 0 || n_faces > RC_MAX_FACES || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
+        c->err = "raycast_build_triangles: bad vertex / face arrays";
+        return IMMESH_E_INVAL;
+    }
+    for (int64_t i = 0; i < 3 * n_faces; i++)
+        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
+            c->err = "raycast_build_triangles: face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
+                     std::to_string(n_vtx) + ")";
+            return IMMESH_E_INVAL;
+        }
+    return 0;
+}
+
+// the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)
+int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
+    immesh_ctx* c = r->ctx;
+    hipStream_t s = r->s;
+    r->built = false; r->have_cast = false; r->n_points = 0;
+    int rc;
+    const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n_faces, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n_faces, 1))) + 256;
+    if ((rc = rc_grow(r, r->flag, (size_t)n_faces * 4))) return rc;
+    if ((rc = rc_grow(r, r->off, (size_t)n_faces * 4))) return rc;
+    if ((rc = rc_grow(r, r->ids, (size_t)n_faces * 4))) return rc;
+    if ((rc = rc_grow(r, r->box, (size_t)n_faces * 24))) return rc;
+    if ((rc = rc_grow(r, r->bounds, 32))) return rc;
+    if ((rc = rc_grow(r, r->temp, temp_bytes))) return rc;
+    const float* vtx = (const float*)r->vtx.p;
+    const int32_t* faces = (const int32_t*)r->faces.p;
+    uint32_t* bounds = (uint32_t*)r->bounds.p;
+    int64_t* d_n_in = (int64_t*)(bounds + 6);
+    HIPCHK(c, hipEventRecord(r->ev[0], s));
+    HIPCHK(c, hipMemsetAsync(bounds, 0xFF, 12, s));
+    HIPCHK(c, hipMemsetAsync(bounds + 3, 0, 20, s));
+    int64_t n_in = 0;
+    if (n_faces > 0) {
+        rc_launch_mark(s, vtx, n_vtx, faces, n_faces, (int32_t*)r->flag.p);
+        rd_scan_i32(s, r->temp.p, r->temp.bytes, (const int32_t*)r->flag.p, (int32_t*)r->off.p, n_faces);
+        rc_launch_compact(s, vtx, faces, n_faces, (const int32_t*)r->flag.p, (const int32_t*)r->off.p, (int32_t*)r->ids.p, (float*)r->box.p, bounds, d_n_in);
+        HIPCHK(c, hipMemcpyAsync(r->h_small, d_n_in, 8, hipMemcpyDeviceToHost, s));   // the one count the host needs: it sizes the tree
+        HIPCHK(c, hipStreamSynchronize(s));
+        n_in = r->h_small[0];
+    }
+    if (n_in > 0) {
+        if ((rc = rc_grow(r, r->code_a, (size_t)n_in * 8))) return rc;
+        if ((rc = rc_grow(r, r->code_b, (size_t)n_in * 8))) return rc;
+        if ((rc = rc_grow(r, r->pos_a, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(r, r->pos_b, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(r, r->leaf, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(r, r->nodes, (size_t)n_in * sizeof(RcNode)))) return rc;
+        RcNode* nodes = (RcNode*)r->nodes.p;
+        if (n_in == 1) {
+            rc_launch_single(s, (const float*)r->box.p, (const int32_t*)r->ids.p, nodes);
+        } else {
+            rc_launch_codes(s, (const float*)r->box.p, n_in, bounds, (unsigned long long*)r->code_a.p, (int32_t*)r->pos_a.p);
+            sort_pairs_u64(s, r->temp.p, r->temp.bytes, (const unsigned long long*)r->code_a.p, (unsigned long long*)r->code_b.p, (const int32_t*)r->pos_a.p,
+                           (int32_t*)r->pos_b.p, (int)n_in, RC_CODE_BITS);
+            rc_launch_hierarchy(s, (const unsigned long long*)r->code_b.p, (const int32_t*)r->ids.p, (const int32_t*)r->pos_b.p, n_in, nodes, (int32_t*)r->leaf.p);
+            rc_launch_refit(s, (const float*)r->box.p, (const int32_t*)r->pos_b.p, (const int32_t*)r->leaf.p, n_in, nodes);
+        }
+    }
+    HIPCHK(c, hipEventRecord(r->ev[1], s));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);
+    r->n_vtx = n_vtx; r->n_faces = n_faces; r->n_in = n_in;
+    r->built = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int immesh_ray_frame_from_state(const immesh_config* cfg, const double* state, immesh_ray_frame* frame) {
+    if (!cfg || !state || !frame) return IMMESH_E_INVAL;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++)
+            frame->rot[3 * i + j] = (state[3 * i] * cfg->extR[j] + state[3 * i + 1] * cfg->extR[3 + j]) + state[3 * i + 2] * cfg->extR[6 + j];
+        frame->pos[i] = ((state[3 * i] * cfg->extT[0] + state[3 * i + 1] * cfg->extT[1]) + state[3 * i + 2] * cfg->extT[2]) + state[9 + i];
+    }
+    return 0;
+}
+
+immesh_raycaster* immesh_raycaster_create(immesh_ctx* ctx) {
+    if (!ctx) return nullptr;
+    (void)hipSetDevice(ctx->cfg.device);
+    immesh_raycaster* r = new immesh_raycaster();
+    r->ctx = ctx;
+    bool ok = hipStreamCreateWithFlags(&r->s, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 6 && ok; i++) ok = hipEventCreate(&r->ev[i]) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&r->h_small, 32) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ctx->err = "immesh_raycaster_create: stream / event / pinned allocation failed";
+        immesh_raycaster_destroy(r);
+        return nullptr;
+    }
+    return r;
+}
+
+void immesh_raycaster_destroy(immesh_raycaster* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->ctx->cfg.device);
+    if (r->s) (void)hipStreamSynchronize(r->s);
+    for (RcBuf* b : {&r->vtx, &r->faces, &r->nodes, &r->flag, &r->off, &r->ids, &r->box, &r->bounds, &r->code_a, &r->code_b, &r->pos_a, &r->pos_b, &r->leaf,
+                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small})
+        if (b->p) (void)hipFree(b->p);
+    for (hipEvent_t e : r->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (r->h_small) (void)hipHostFree(r->h_small);
+    if (r->s) (void)hipStreamDestroy(r->s);
+    delete r;
+}
+
+int immesh_raycast_build_triangles(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    int rc = rc_check_soup(r, vtx_xyz, n_vtx, faces, n_faces);   // before anything is touched: a refused soup leaves the built snapshot as it was
+    if (rc) return rc;
+    (void)hipSetDevice(c->cfg.device);
+    r->built = false;
+    if ((rc = rc_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
+    if ((rc = rc_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
+    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
+    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
+    return rc_build(r, n_vtx, n_faces);
+}
+
+int immesh_raycast_build_mesh(immesh_raycaster* r, double smooth_factor, int32_t knn) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    int64_t nv = 0, nf = 0;
+    int rc = immesh_mesh_export(c, smooth_factor, knn, &nv, &nf);   // synchronises the ctx stream: the arrays are complete
+    if (rc) return rc;
+    if (nf > RC_MAX_FACES) { c->err = "raycast_build_mesh: more than 2^30 faces"; return IMMESH_E_CAPACITY; }
+    const MeshHost& h = c->mesh_host;
+    (void)hipSetDevice(c->cfg.device);
+    r->built = false;
+    if ((rc = rc_grow(r, r->vtx, (size_t)nv * 12))) return rc;
+    if ((rc = rc_grow(r, r->faces, (size_t)nf * 12))) return rc;
+    // the snapshot: the caster's own copies, complete before this call returns (rc_build synchronises), so the next export may overwrite its arrays
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, h.exp_vtx, (size_t)nv * 12, hipMemcpyDeviceToDevice, r->s));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, h.exp_faces, (size_t)nf * 12, hipMemcpyDeviceToDevice, r->s));
+    return rc_build(r, nv, nf);
+}
+
+int immesh_raycast_sizes(immesh_raycaster* r, int64_t* n_vtx, int64_t* n_faces, int64_t* n_in_tree) {
+    if (!r) return IMMESH_E_INVAL;
+    if (!r->built) { r->ctx->err = "raycast_sizes: no hierarchy has been built"; return IMMESH_E_INVAL; }
+    if (n_vtx) *n_vtx = r->n_vtx;
+    if (n_faces) *n_faces = r->n_faces;
+    if (n_in_tree) *n_in_tree = r->n_in;
+    return 0;
+}
+
+int immesh_raycast(immesh_raycaster* r, const immesh_ray_frame* frame, const float* dirs, const float* origins, int64_t n_rays, double t_min, double t_max,
+                   int32_t mode, float* t_out, int32_t* face_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    if (!r->built) { c->err = "raycast: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    if (!frame) { c->err = "raycast: frame is NULL"; return IMMESH_E_INVAL; }
+    if (n_rays < 0 || n_rays > (int64_t)0x7FFFFFFE || (n_rays > 0 && !dirs)) { c->err = "raycast: bad ray arrays"; return IMMESH_E_INVAL; }
+    if (mode != IMMESH_RAY_NEAREST && mode != IMMESH_RAY_ANY) { c->err = "raycast: unknown mode " + std::to_string(mode); return IMMESH_E_INVAL; }
+    if (!(t_min >= 0.0) || !(t_min < t_max) || !std::isfinite(t_max)) { c->err = "raycast: need 0 <= t_min < t_max, both finite"; return IMMESH_E_INVAL; }
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(frame->rot[i])) { c->err = "raycast: frame rotation is not finite"; return IMMESH_E_INVAL; }
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(frame->pos[i])) { c->err = "raycast: frame position is not finite"; return IMMESH_E_INVAL; }
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t s = r->s;
+    int rc;
+    const int m = mode == IMMESH_RAY_NEAREST ? 0 : 1;   // an ANY cast leaves the last NEAREST cast's rays and distances where the reinforce pass reads them
+    if (m == 0) { r->have_cast = false; r->n_points = 0; }
+    if ((rc = rc_grow(r, r->dirs[m], (size_t)n_rays * 12))) return rc;
+    if (origins && (rc = rc_grow(r, r->org[m], (size_t)n_rays * 12))) return rc;
+    if ((rc = rc_grow(r, r->t[m], (size_t)n_rays * 4))) return rc;
+    if ((rc = rc_grow(r, r->face[m], (size_t)n_rays * 4))) return rc;
+    RcFrame fr;
+    std::memcpy(fr.rot, frame->rot, sizeof(fr.rot));
+    std::memcpy(fr.pos, frame->pos, sizeof(fr.pos));
+    if (n_rays > 0) {
+        HIPCHK(c, hipMemcpyAsync(r->dirs[m].p, dirs, (size_t)n_rays * 12, hipMemcpyHostToDevice, s));
+        if (origins) HIPCHK(c, hipMemcpyAsync(r->org[m].p, origins, (size_t)n_rays * 12, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(c, hipEventRecord(r->ev[2], s));
+    rc_launch_cast(s, fr, (const float*)r->dirs[m].p, origins ? (const float*)r->org[m].p : nullptr, n_rays, t_min, t_max, mode, (const float*)r->vtx.p,
+                   (const int32_t*)r->faces.p, (const RcNode*)r->nodes.p, r->n_in, (float*)r->t[m].p, (int32_t*)r->face[m].p);
+    HIPCHK(c, hipEventRecord(r->ev[3], s));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&r->ms[1], r->ev[2], r->ev[3]);
+    if (t_out && n_rays > 0) HIPCHK(c, hipMemcpy(t_out, r->t[m].p, (size_t)n_rays * 4, hipMemcpyDeviceToHost));
+    if (face_out && n_rays > 0) HIPCHK(c, hipMemcpy(face_out, r->face[m].p, (size_t)n_rays * 4, hipMemcpyDeviceToHost));
+    if (m == 0) { r->have_cast = true; r->have_origins = origins != nullptr; r->n_rays = n_rays; r->frame = fr; }
+    return 0;
+}
+
+int immesh_raycast_points(immesh_raycaster* r, double downsample_res, float* xyz_out, int64_t cap, int64_t* n_out) {
+    if (!r) return IMMESH_E_INVAL;
+    immesh_ctx* c = r->ctx;
+    if (std::isnan(downsample_res)) { c->err = "raycast_points: downsample_res is NaN"; return IMMESH_E_INVAL; }
+    if (!r->have_cast) { c->err = "raycast_points: no NEAREST cast since the last build"; return IMMESH_E_INVAL; }
+    (void)hipSetDevice(c->cfg.device);
+    hipStream_t s = r->s;
+    const int64_t n = r->n_rays;
+    const float res = (float)downsample_res;
+    r->n_points = 0;
+    if (n > 0) {
+        int rc;
+        if ((rc = rc_grow(r, r->temp, rd_scan_temp_bytes(1, 1, n) + 256))) return rc;
+        if ((rc = rc_grow(r, r->pts, (size_t)n * 12))) return rc;
+        if ((rc = rc_grow(r, r->keep, (size_t)n * 4))) return rc;
+        if ((rc = rc_grow(r, r->koff, (size_t)n * 4))) return rc;
+        if ((rc = rc_grow(r, r->out, (size_t)n * 12))) return rc;
+        if ((rc = rc_grow(r, r->small, 16))) return rc;
+        uint32_t mask = 0;
+        if (res > 0.0f) {
+            uint64_t tab = 1024;
+            while (tab < 2 * (uint64_t)n) tab <<= 1;
+            mask = (uint32_t)(tab - 1);
+            if ((rc = rc_grow(r, r->cells, (size_t)n * 12))) return rc;
+            if ((rc = rc_grow(r, r->slot, (size_t)n * 4))) return rc;
+            if ((rc = rc_grow(r, r->tab, (size_t)tab * 8))) return rc;
+        }
+        const float* t = (const float*)r->t[0].p;
+        int32_t* keep = (int32_t*)r->keep.p;
+        HIPCHK(c, hipEventRecord(r->ev[4], s));
+        rc_launch_points(s, r->frame, (const float*)r->dirs[0].p, r->have_origins ? (const float*)r->org[0].p : nullptr, n, res, t, (float*)r->pts.p,
+                         (float*)r->cells.p, keep);
+        if (res > 0.0f) {   // the renderer's thinning, as it is: a count, a depth array (t: -1 = no point) and cells
+            int32_t* tab_rep = (int32_t*)r->tab.p;
+            uint32_t* tab_min = (uint32_t*)(tab_rep + (size_t)mask + 1);
+            HIPCHK(c, hipMemsetAsync(tab_rep, 0xFF, ((size_t)mask + 1) * 8, s));   // rep -1, min 0xFFFFFFFF
+            rd_launch_hash_insert(s, n, t, (const float*)r->cells.p, tab_rep, tab_min, mask, (uint32_t*)r->slot.p);
+            rd_launch_hash_keep(s, n, t, tab_min, (const uint32_t*)r->slot.p, keep);
+        }
+        rd_scan_i32(s, r->temp.p, r->temp.bytes, keep, (int32_t*)r->koff.p, n);
+        rd_launch_compact(s, n, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
+        HIPCHK(c, hipEventRecord(r->ev[5], s));
+        HIPCHK(c, hipMemcpyAsync(r->h_small + 1, r->small.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(s));
+        r->n_points = r->h_small[1];
+        (void)hipEventElapsedTime(&r->ms[2], r->ev[4], r->ev[5]);
+    }
+    if (n_out) *n_out = r->n_points;
+    if (!xyz_out || r->n_points == 0) return 0;
+    if (cap < r->n_points) {
+        c->err = "raycast_points: cap " + std::to_string(cap) + " < " + std::to_string(r->n_points) + " points";
+        return IMMESH_E_CAPACITY;
+    }
+    HIPCHK(c, hipMemcpy(xyz_out, r->out.p, (size_t)r->n_points * 12, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int immesh_raycaster_last_timing(immesh_raycaster* r, float ms[3]) {
+    if (!r || !ms) return IMMESH_E_INVAL;
+    ms[0] = r->ms[0]; ms[1] = r->ms[1]; ms[2] = r->ms[2];
+    return 0;
+}
+
+}  // extern "C"
