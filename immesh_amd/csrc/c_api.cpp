@@ -210,6 +210,9 @@ static int settle(immesh_ctx* c, bool synced = false) {
     return check_overflow(c);
 }
 
+// The prior covariance's pose block must be finite and invertible (imh::pose_block_usable): refused with one text on every route, before any launch.
+static int singular_prior(immesh_ctx* c) { c->err = "singular prior covariance"; return IMMESH_E_INVAL; }
+
 static int run_residual_pass(immesh_ctx* c, const float* d_pts, int n, const imh::State& st, const double* prior_cov) {
     ScanParams sp;
     make_scan_params(c, st, prior_cov, sp);
@@ -255,7 +258,7 @@ static int register_enqueue_chain(immesh_ctx* c, const float* d_pts, int n_ds, c
         if (it == 0) {
             double p11[36];
             for (int r = 0; r < 6; r++) for (int q = 0; q < 6; q++) p11[r * 6 + q] = st.cov[r * 18 + q];
-            if (!imh::invert(p11, a.mat, 6)) { c->err = "singular prior covariance"; return IMMESH_E_INVAL; }
+            if (!imh::invert(p11, a.mat, 6)) return singular_prior(c);
             for (int i = 0; i < 12; i++)
                 for (int q = 0; q < 6; q++) { double sacc = 0; for (int k = 0; k < 6; k++) sacc += st.cov[(6 + i) * 18 + k] * a.mat[k * 6 + q]; a.mat[36 + i * 6 + q] = sacc; }
         }
@@ -356,6 +359,7 @@ static int register_device(immesh_ctx* c, const float* d_pts, int n_ds, const im
         if (res_mean) *res_mean = o[RES_N_MATCH] > 0 ? o[RES_SUM_DIS] / o[RES_N_MATCH] : 0.0;
         if (ekf.step(o + RES_HTH, o + RES_HTZ, prior, st, it, max_iter)) break;
     }
+    if (ekf.singular) return singular_prior(c);   // (an 18 x 18 inverse did not exist; `st` is as the caller gave it)
     c->cnt.n_iter += iters;
     c->cnt.n_ds = n_ds;
     c->last_n_ds = n_ds;
@@ -366,6 +370,7 @@ static int register_device(immesh_ctx* c, const float* d_pts, int n_ds, const im
 int immesh_register(immesh_ctx* c, const float* pts, int32_t n_ds, const double* state_prior, double* state_inout, int32_t* n_iter_out,
                     int32_t* n_match_out, double* res_mean_out, float* eff_pts_body, float* eff_norm_dis) {
     if (!c || !pts || n_ds <= 0 || n_ds > c->cap_scan || !state_prior || !state_inout) { if (c) c->err = "bad arguments"; return IMMESH_E_INVAL; }
+    if (!imh::pose_block_usable(state_inout + 24)) return singular_prior(c);
     (void)hipSetDevice(c->cfg.device);
     ProfBind _pb(c);
     c->ds_gate_ok = false;
@@ -653,6 +658,7 @@ int immesh_process_scan(immesh_ctx* c, const float* pts_down, int32_t n_ds, cons
         if (c) c->err = "bad arguments";
         return IMMESH_E_INVAL;
     }
+    if (!imh::pose_block_usable(state_inout + 24)) return singular_prior(c);
     (void)hipSetDevice(c->cfg.device);
     ProfBind _pb(c);
     c->ds_gate_ok = false;

@@ -88,9 +88,20 @@ inline void state_minus(const State& a, const State& b, double* out) {  // a - b
     for (int k = 0; k < 3; k++) { out[3 + k] = a.t[k] - b.t[k]; out[6 + k] = a.vel[k] - b.vel[k]; out[9 + k] = a.bg[k] - b.bg[k]; out[12 + k] = a.ba[k] - b.ba[k]; out[15 + k] = a.g[k] - b.g[k]; }
 }
 
-// One Kalman step from the reduced normal equations.  Returns true when the EKF must stop (covariance updated).
+// The input contract of every registration route (immesh_register / immesh_process_scan): the 6 x 6 pose block of the prior covariance is finite
+// and invertible.  The device forms eliminate on it without pivoting, so it is checked here, on the host, before anything is launched.
+inline bool pose_block_usable(const double* cov /*18 x 18*/) {
+    double p11[36], inv[36];
+    for (int r = 0; r < 6; r++)
+        for (int q = 0; q < 6; q++) { p11[r * 6 + q] = cov[r * 18 + q]; if (!std::isfinite(p11[r * 6 + q])) return false; }
+    return invert(p11, inv, 6);
+}
+
+// One Kalman step from the reduced normal equations.  Returns true when the EKF must stop (covariance updated, or `singular` set: an 18 x 18
+// inverse did not exist, the state is as it was on entry).
 struct EkfLoop {
     int rematch_num = 0;
+    bool singular = false;
     double G[324];
     double covinv[324];      // state.cov is the prior covariance for every iteration of a scan (overwritten only at stop): invert it once
     bool have_covinv = false;
@@ -101,9 +112,9 @@ struct EkfLoop {
         for (int r = 0; r < 6; r++)
             for (int c = 0; c < 6; c++) HTH18[r * 18 + c] = HTH[r * 6 + c];
         double S[324], K1[324];
-        if (!have_covinv) { invert(st.cov, covinv, 18); have_covinv = true; }
+        if (!have_covinv) { if (!invert(st.cov, covinv, 18)) { singular = true; return true; } have_covinv = true; }
         for (int k = 0; k < 324; k++) S[k] = HTH18[k] + covinv[k];
-        invert(S, K1, 18);
+        if (!invert(S, K1, 18)) { singular = true; return true; }
         for (int r = 0; r < 18; r++)
             for (int c = 0; c < 6; c++) {
                 double s = 0;

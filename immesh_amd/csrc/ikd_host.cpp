@@ -222,6 +222,7 @@ int immesh_ikd_register(immesh_ctx* c, const float* pts_down_body_xyz, int32_t n
         nearest_search_en = ekf.rematch_num != rematch_before;   // "Rematch Judgement", voxel_mapping.cpp:1626-1632
         if (stop) break;
     }
+    if (ekf.singular) { c->err = "singular prior covariance"; return IMMESH_E_INVAL; }   // (state_inout stays as the caller gave it)
     imh::store_state(st, state_inout);
     if (n_iter_out) *n_iter_out = iters;
     if (match_idx || normals_pd2) {   // m_laserCloudOri / m_corr_normvect of the last iteration, ascending scan index

@@ -91,7 +91,11 @@ int immesh_map_build(immesh_ctx* ctx, const float* pts_body_xyz, int64_t n, cons
  * state_inout = `state` (in: prior, out: posterior incl. covariance).  Optional outputs (may be NULL):
  *   n_iter_out, n_match_out (m_effct_feat_num of the last iteration), res_mean_out (m_res_mean_last),
  *   eff_pts_body  [n_ds*3]  m_laserCloudOri (matched body points, match order = ascending scan index),
- *   eff_norm_dis  [n_ds*4]  m_corr_normvect  (float normal xyz + residual in .intensity). */
+ *   eff_norm_dis  [n_ds*4]  m_corr_normvect  (float normal xyz + residual in .intensity).
+ * Input contract: the 6 x 6 pose block (rotation, translation) of state_inout's covariance is finite and invertible.  It is checked on the host
+ * before anything is launched; a prior that fails returns IMMESH_E_INVAL ("singular prior covariance") on every route -- the resident grid, the
+ * per-pass chain and the host loop, which also refuses an 18 x 18 covariance it cannot invert -- leaves state_inout untouched and leaves the
+ * context as it was: the next registration on it equals a fresh context's. */
 int immesh_register(immesh_ctx* ctx, const float* pts_down_body_xyz, int32_t n_ds, const double* state_prior, double* state_inout,
                     int32_t* n_iter_out, int32_t* n_match_out, double* res_mean_out, float* eff_pts_body, float* eff_norm_dis);
 
@@ -202,7 +206,9 @@ int immesh_mesh_display_vertices(immesh_ctx* ctx, const int32_t* vertex_ids, int
  * do_mesh: IMMESH_MESH_OFF = registration + map update only, IMMESH_MESH_SYNC = mesh synchronously, IMMESH_MESH_ASYNC = queue the mesh job
  * and return (see immesh_mesh_wait).  IMMESH_MESH_ASYNC, or IMMESH_SCAN_NOWAIT or-ed in, also returns without waiting for the map update: the
  * pose is final when the call returns, map growth finishes on the stream ahead of the next call's work, and a capacity error of that update is
- * reported by the next call on the context (immesh_last_timing / immesh_counters wait for it). */
+ * reported by the next call on the context (immesh_last_timing / immesh_counters wait for it).
+ * The input contract of immesh_register holds here too: a prior covariance whose pose block is not finite and invertible is refused with
+ * IMMESH_E_INVAL ("singular prior covariance") before anything is launched; state_inout, the map and the mesh are untouched. */
 #define IMMESH_MESH_OFF 0
 #define IMMESH_MESH_SYNC 1
 #define IMMESH_MESH_ASYNC 2
