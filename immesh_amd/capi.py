@@ -166,6 +166,13 @@ def ray_frame(rot=None, pos=None):
     return fr
 
 
+class ClosestStats(C.Structure):
+    """immesh_closest_stats (include/immesh_closest.h): the last closest-point query reduced on the device"""
+    _fields_ = [("n_points", C.c_int64), ("n_with_face", C.c_int64), ("n_not_finite", C.c_int64), ("n_no_face", C.c_int64), ("n_overflow", C.c_int64),
+                ("sum_dist", C.c_double), ("sum_dist2", C.c_double), ("mean", C.c_double), ("rms", C.c_double),
+                ("max_dist", C.c_float), ("bin_width", C.c_float)]
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -752,6 +759,37 @@ class HotPath:
         ms = (C.c_float * 3)()
         self._check(f(self.raycaster(), ms), "raycaster_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # -- point-to-mesh distances on the caster (include/immesh_closest.h) ---------------------------------------------------------------------------
+    def closest_points(self, pts, max_dist, frame=None, want=("d2", "dist", "face", "xyz", "side")):
+        """immesh_closest_points: pts (n, 3) in the world (frame None) or in the sensor frame -> dict of the wanted outputs: d2 (n,) float64,
+        dist (n,) float32, face (n,) int32 (-1: none), xyz (n, 3) float32, side (n,) int8"""
+        f = self.lib.immesh_closest_points
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.c_double] + [C.c_void_p] * 5
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        out = {"d2": np.empty(n, np.float64), "dist": np.empty(n, np.float32), "face": np.empty(n, np.int32), "xyz": np.empty((n, 3), np.float32),
+               "side": np.empty(n, np.int8)}
+        out = {k: v for k, v in out.items() if k in want}
+        self._check(f(self.raycaster(), None if frame is None else C.byref(frame), _ptr(p), n, max_dist,
+                      *[_ptr(out.get(k)) for k in ("d2", "dist", "face", "xyz", "side")]), "closest_points")
+        return out
+
+    def closest_stats(self, bin_width, n_bins):
+        """immesh_closest_reduce over the caster's last query -> (ClosestStats, histogram (n_bins,) int64)"""
+        f = self.lib.immesh_closest_reduce; f.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(ClosestStats), C.c_void_p]; f.restype = C.c_int
+        st = ClosestStats()
+        hist = np.zeros(max(int(n_bins), 0) if int(n_bins) <= (1 << 20) else 0, np.int64)      # (a bad size is the library's to reject)
+        self._check(f(self.raycaster(), bin_width, n_bins, C.byref(st), _ptr(hist)), "closest_reduce")
+        return st, hist
+
+    def closest_timing(self):
+        """device milliseconds of the last (query, reduction)"""
+        f = self.lib.immesh_closest_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "closest_last_timing")
+        return float(ms[0]), float(ms[1])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

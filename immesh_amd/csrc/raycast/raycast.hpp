@@ -27,6 +27,16 @@ static_assert(sizeof(RcNode) == 64, "RcNode layout");
 
 struct RcFrame { double rot[9], pos[3]; };
 
+// one partial of the closest-point reduction, and its folded result
+struct ClStatsDev {
+    double sum, sum2;
+    int64_t n_face, n_not_finite, n_no_face;
+    float max_dist;
+    int32_t pad;
+};
+static_assert(sizeof(ClStatsDev) == 48, "ClStatsDev layout");
+constexpr int CL_LDS_BINS = 1024;
+
 // build -----------------------------------------------------------------------------------------------------------------------------------
 // flag[f] = 1 when face f enters the tree (indices in range, nine finite coordinates)
 void rc_launch_mark(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, int32_t* flag);
@@ -51,3 +61,54 @@ void rc_launch_cast(hipStream_t s, const RcFrame& fr, const float* dirs, const f
 // reinforce: pts[3 i] of the hit rays (t[i] >= 0), cells when res > 0, keep[i] = res > 0 ? 0 : hit
 void rc_launch_points(hipStream_t s, const RcFrame& fr, const float* dirs, const float* origins, int64_t n_rays, float res, const float* t, float* pts,
                       float* cells, int32_t* keep);
+
+// ---- the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries --------------------
+struct immesh_ctx;
+struct RcBuf {   // grow-only device buffer
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// closest-point queries: allocated at the first query, never before
+struct RcClosest {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // query, reduction: begin / end
+    RcBuf pts, d2, dist, face, xyz, side, status;              // the last query: its points and its results
+    RcBuf part, hist, res;                                     // the reduction: per-workgroup partials, histogram, folded result
+    ClStatsDev* h_res = nullptr;                               // pinned
+    bool have_query = false;
+    int64_t n_pts = 0;
+    float ms[2] = {0.0f, 0.0f};
+};
+
+struct immesh_raycaster {
+    immesh_ctx* ctx = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // build, cast, reinforce: begin / end
+    int64_t* h_small = nullptr;   // pinned: [0] faces in the tree, [1] reinforced points
+    RcBuf vtx, faces, nodes;                                                       // the built snapshot
+    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
+    RcBuf dirs[2], org[2], t[2], face[2];                                          // the last cast of each mode ([0] NEAREST: the reinforce pass reads it)
+    RcBuf pts, cells, keep, koff, slot, tab, out, small;                           // reinforce
+    bool built = false;
+    int64_t n_vtx = 0, n_faces = 0, n_in = 0;
+    // the last NEAREST cast, as the reinforce pass reads it
+    bool have_cast = false, have_origins = false;
+    int64_t n_rays = 0;
+    RcFrame frame = {};
+    int64_t n_points = 0;
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    RcClosest cl;
+};
+// grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with text in the context
+int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes);
+
+// closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------
+// status[i]: 0 a face, 1 no face within max_dist, 2 the point is not finite.  has_frame == 0: the points are world coordinates.
+void cl_launch_query(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n_pts, double r2, const float* vtx,
+                     const int32_t* faces, const RcNode* nodes, int64_t n_in, double* d2, float* dist, int32_t* face, float* xyz, int8_t* side, uint8_t* status);
+// part[b] = the partial of workgroup b (cl_stats_blocks(n_pts) of them), hist[0 .. n_bins) += the bins, hist[n_bins] += the overflow (hist zeroed by the
+// caller; up to CL_LDS_BINS bins are counted in LDS first);
+// then res[0] = the partials folded in index order
+int64_t cl_stats_blocks(int64_t n_pts);
+void cl_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, int64_t n_pts, float bin_width, int32_t n_bins, ClStatsDev* part,
+                     unsigned long long* hist, ClStatsDev* res);

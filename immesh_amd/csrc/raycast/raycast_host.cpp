@@ -8,34 +8,6 @@
 #include "../render/render.hpp"
 #include "raycast.hpp"
 
-struct RcBuf {   // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct immesh_raycaster {
-    immesh_ctx* ctx = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // build, cast, reinforce: begin / end
-    int64_t* h_small = nullptr;   // pinned: [0] faces in the tree, [1] reinforced points
-    RcBuf vtx, faces, nodes;                                                       // the built snapshot
-    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
-    RcBuf dirs[2], org[2], t[2], face[2];                                          // the last cast of each mode ([0] NEAREST: the reinforce pass reads it)
-    RcBuf pts, cells, keep, koff, slot, tab, out, small;                           // reinforce
-    bool built = false;
-    int64_t n_vtx = 0, n_faces = 0, n_in = 0;
-    // the last NEAREST cast, as the reinforce pass reads it
-    bool have_cast = false, have_origins = false;
-    int64_t n_rays = 0;
-    RcFrame frame = {};
-    int64_t n_points = 0;
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-};
-
-namespace {
-
-constexpr int64_t RC_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;
-
 int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (b.bytes >= bytes) return 0;
@@ -50,6 +22,10 @@ int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) {
     b.bytes = want;
     return 0;
 }
+
+namespace {
+
+constexpr int64_t RC_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;
 
 int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
     immesh_ctx* c = r->ctx;
@@ -158,10 +134,13 @@ void immesh_raycaster_destroy(immesh_raycaster* r) {
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
     for (RcBuf* b : {&r->vtx, &r->faces, &r->nodes, &r->flag, &r->off, &r->ids, &r->box, &r->bounds, &r->code_a, &r->code_b, &r->pos_a, &r->pos_b, &r->leaf,
-                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small})
+                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->cl.pts, &r->cl.d2, &r->cl.dist, &r->cl.face, &r->cl.xyz, &r->cl.side, &r->cl.status, &r->cl.part, &r->cl.hist, &r->cl.res})
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t e : r->ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->cl.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (r->cl.h_res) (void)hipHostFree(r->cl.h_res);
     if (r->h_small) (void)hipHostFree(r->h_small);
     if (r->s) (void)hipStreamDestroy(r->s);
     delete r;

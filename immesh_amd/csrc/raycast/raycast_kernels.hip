@@ -7,15 +7,9 @@
 //   reinforce the hit points and their cells; thinning and compaction are the renderer's launches (render.hpp)
 // Double arithmetic is written in the contract's order; the library builds with -ffp-contract=off, so nothing is fused.
 #include "raycast.hpp"
+#include "raycast_dev.hpp"
 
 namespace {
-
-__device__ __forceinline__ void rc_cross(const double* p, const double* q, double* o) {
-    o[0] = p[1] * q[2] - p[2] * q[1];
-    o[1] = p[2] * q[0] - p[0] * q[2];
-    o[2] = p[0] * q[1] - p[1] * q[0];
-}
-__device__ __forceinline__ double rc_dot(const double* p, const double* q) { return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2]; }
 
 // floats <-> unsigned keys of the same order
 __device__ __forceinline__ uint32_t rc_key(float v) {
