@@ -425,6 +425,10 @@ class HotPath:
             g = self.lib.immesh_colourer_destroy; g.argtypes = [C.c_void_p]; g.restype = None
             g(self._colourer)
             self._colourer = None
+        if getattr(self, "_cloud_index", None):              # the cloud index goes before its context (and before the caster whose samples it reads)
+            g = self.lib.immesh_cloud_index_destroy; g.argtypes = [C.c_void_p]; g.restype = None
+            g(self._cloud_index)
+            self._cloud_index = None
         if getattr(self, "_raycaster", None):                # the ray caster goes before its context
             g = self.lib.immesh_raycaster_destroy; g.argtypes = [C.c_void_p]; g.restype = None
             g(self._raycaster)
@@ -790,6 +794,89 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "closest_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- mesh-to-cloud distances (include/immesh_nearest.h) ------------------------------------------------------------------------------------------
+    def cloud_index(self):
+        """the context's cloud index (created at first use, destroyed by close())"""
+        if getattr(self, "_cloud_index", None) is None:
+            f = self.lib.immesh_cloud_index_create; f.argtypes = [C.c_void_p]; f.restype = C.c_void_p
+            x = f(self.ctx)
+            if not x:
+                self._check(-1, "cloud_index_create")
+            self._cloud_index = C.c_void_p(x)
+        return self._cloud_index
+
+    def cloud_index_build(self, xyz):
+        """immesh_cloud_index_build on a host cloud (n, 3) -> (points given, points in the hierarchy)"""
+        f = self.lib.immesh_cloud_index_build; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]; f.restype = C.c_int
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._check(f(self.cloud_index(), _ptr(p), len(p)), "cloud_index_build")
+        g = self.lib.immesh_cloud_index_sizes; g.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; g.restype = C.c_int
+        n, ni = C.c_int64(0), C.c_int64(0)
+        self._check(g(self.cloud_index(), C.byref(n), C.byref(ni)), "cloud_index_sizes")
+        return n.value, ni.value
+
+    def mesh_sample(self, density, seed=0, fetch=True):
+        """immesh_mesh_sample on the caster's snapshot -> (xyz (n, 3) float32, face (n,) int32), or the count alone with fetch=False; the samples stay
+        on the device for nearest_samples"""
+        f = self.lib.immesh_mesh_sample
+        f.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), density, seed, None, None, 0, C.byref(n)), "mesh_sample")
+        if not fetch:
+            return n.value
+        xyz, face = np.zeros((n.value, 3), np.float32), np.zeros(n.value, np.int32)
+        self._check(f(self.raycaster(), density, seed, _ptr(xyz), _ptr(face), n.value, C.byref(n)), "mesh_sample")
+        return xyz, face
+
+    def mesh_sample_timing(self):
+        """device milliseconds of the last sampling (counts, scan + emit)"""
+        f = self.lib.immesh_mesh_sample_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "mesh_sample_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def _nearest_outputs(self, n, want):
+        out = {"d2": np.empty(n, np.float64), "dist": np.empty(n, np.float32), "index": np.empty(n, np.int32), "xyz": np.empty((n, 3), np.float32)}
+        return {k: v for k, v in out.items() if k in want}
+
+    def nearest_points(self, pts, max_dist, frame=None, want=("d2", "dist", "index", "xyz")):
+        """immesh_nearest_points: pts (n, 3) in the world (frame None) or in the sensor frame -> dict of the wanted outputs: d2 (n,) float64,
+        dist (n,) float32, index (n,) int32 (-1: none), xyz (n, 3) float32"""
+        f = self.lib.immesh_nearest_points
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.c_double] + [C.c_void_p] * 4
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        out = self._nearest_outputs(len(p), want)
+        self._check(f(self.cloud_index(), None if frame is None else C.byref(frame), _ptr(p), len(p), max_dist,
+                      *[_ptr(out.get(k)) for k in ("d2", "dist", "index", "xyz")]), "nearest_points")
+        return out
+
+    def nearest_samples(self, max_dist, want=("d2", "dist", "index", "xyz")):
+        """immesh_nearest_samples: the caster's last samples against the index, without a round trip -> the dict of nearest_points"""
+        f = self.lib.immesh_nearest_samples; f.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4; f.restype = C.c_int
+        g = self.lib.immesh_mesh_sample_count; g.argtypes = [C.c_void_p, C.c_void_p]; g.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(g(self.raycaster(), C.byref(n)), "mesh_sample_count")
+        n = n.value
+        out = self._nearest_outputs(n, want)
+        self._check(f(self.cloud_index(), self.raycaster(), max_dist, *[_ptr(out.get(k)) for k in ("d2", "dist", "index", "xyz")]), "nearest_samples")
+        return out
+
+    def nearest_stats(self, bin_width, n_bins):
+        """immesh_nearest_reduce over the index's last query -> (ClosestStats, histogram (n_bins,) int64); n_with_face reads: with a neighbour"""
+        f = self.lib.immesh_nearest_reduce; f.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(ClosestStats), C.c_void_p]; f.restype = C.c_int
+        st = ClosestStats()
+        hist = np.zeros(max(int(n_bins), 0) if int(n_bins) <= (1 << 20) else 0, np.int64)      # (a bad size is the library's to reject)
+        self._check(f(self.cloud_index(), bin_width, n_bins, C.byref(st), _ptr(hist)), "nearest_reduce")
+        return st, hist
+
+    def nearest_timing(self):
+        """device milliseconds of the last (build, query, reduction)"""
+        f = self.lib.immesh_nearest_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.cloud_index(), ms), "nearest_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

@@ -80,6 +80,17 @@ struct RcClosest {
     float ms[2] = {0.0f, 0.0f};
 };
 
+// samples of the snapshot (include/immesh_nearest.h): allocated at the first immesh_mesh_sample, never before
+struct RcSample {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // counts, scan + emit: begin / end
+    hipEvent_t done = nullptr;                                 // recorded behind the emit launch: a cloud index's stream waits on it
+    RcBuf cnt, off, total, xyz, face;                          // k_f, its exclusive prefix sum, the int64 total; the last samples
+    int64_t* h_total = nullptr;                                // pinned
+    bool have = false;                                         // samples of the current snapshot exist
+    int64_t n = 0;
+    float ms[2] = {0.0f, 0.0f};
+};
+
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
     hipStream_t s = nullptr;
@@ -98,6 +109,7 @@ struct immesh_raycaster {
     int64_t n_points = 0;
     float ms[3] = {0.0f, 0.0f, 0.0f};
     RcClosest cl;
+    RcSample sm;
 };
 // grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with text in the context
 int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes);
@@ -112,3 +124,39 @@ void cl_launch_query(hipStream_t s, const RcFrame& fr, int has_frame, const floa
 int64_t cl_stats_blocks(int64_t n_pts);
 void cl_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, int64_t n_pts, float bin_width, int32_t n_bins, ClStatsDev* part,
                      unsigned long long* hist, ClStatsDev* res);
+
+// ---- mesh-to-cloud distances (include/immesh_nearest.h): nearest_host.cpp owns the index and the sampler's host side ---------------------------------
+// An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi.  The build runs cn_launch_mark / cn_launch_compact and then
+// the caster's own launches (rc_launch_codes, the pair sort, rc_launch_hierarchy, rc_launch_refit; rc_launch_single for one point), one point per leaf.
+struct immesh_cloud_index {
+    immesh_ctx* ctx = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // build, query, reduction: begin / end
+    int64_t* h_small = nullptr;   // pinned: [0] points in the tree
+    ClStatsDev* h_res = nullptr;  // pinned
+    RcBuf pts, nodes;                                                              // the built cloud
+    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
+    RcBuf q_pts, d2, dist, index, xyz, status;                                     // the last query: its host-copied points and its results
+    RcBuf part, hist, res;                                                         // the reduction
+    bool built = false, have_query = false;
+    int64_t n_pts = 0, n_in = 0, n_query = 0;
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+};
+
+// flag[i] = 1 when cloud point i enters the tree (three finite floats)
+void cn_launch_mark(hipStream_t s, const float* xyz, int64_t n_pts, int32_t* flag);
+// ids[off[i]] = i for the marked points, box[6 j] = (c, c) of ids[j]; bounds[6] and n_in[0] as rc_launch_compact leaves them
+void cn_launch_compact(hipStream_t s, const float* xyz, int64_t n_pts, const int32_t* flag, const int32_t* off, int32_t* ids, float* box, uint32_t* bounds,
+                       int64_t* n_in);
+// nearest cloud point of every query; status[i] as cl_launch_query writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
+// cl_launch_stats reduces it.  n_in == 0 reads no node.  Two entries: points copied from the host, with an optional frame; a device array of world floats.
+void cn_launch_nearest(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n, double r2, const float* cloud, const RcNode* nodes,
+                       int64_t n_in, double* d2, float* dist, int32_t* index, float* xyz, uint8_t* status);
+void cn_launch_nearest_world(hipStream_t s, const float* world_pts, int64_t n, double r2, const float* cloud, const RcNode* nodes, int64_t n_in, double* d2,
+                             float* dist, int32_t* index, float* xyz, uint8_t* status);
+// the sampler: cnt[f] = min(k_f, 2^31 - 1), total[0] (zeroed by the caller) += k_f
+void ms_launch_count(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, double density, uint64_t seed, int32_t* cnt,
+                     unsigned long long* total);
+// sample s of n_samples (the total, below 2^31 - 1): sample s - off[f] of the face f it falls into by the offsets
+void ms_launch_emit(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, uint64_t seed, const int32_t* off, int64_t n_samples, float* xyz,
+                    int32_t* face);

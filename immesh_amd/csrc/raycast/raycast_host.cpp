@@ -47,6 +47,7 @@ int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
     immesh_ctx* c = r->ctx;
     hipStream_t s = r->s;
     r->built = false; r->have_cast = false; r->n_points = 0;
+    r->sm.have = false;   // samples belong to the snapshot they were drawn from
     int rc;
     const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n_faces, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n_faces, 1))) + 256;
     if ((rc = rc_grow(r, r->flag, (size_t)n_faces * 4))) return rc;
@@ -134,13 +135,17 @@ void immesh_raycaster_destroy(immesh_raycaster* r) {
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
     for (RcBuf* b : {&r->vtx, &r->faces, &r->nodes, &r->flag, &r->off, &r->ids, &r->box, &r->bounds, &r->code_a, &r->code_b, &r->pos_a, &r->pos_b, &r->leaf,
-                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->cl.pts, &r->cl.d2, &r->cl.dist, &r->cl.face, &r->cl.xyz, &r->cl.side, &r->cl.status, &r->cl.part, &r->cl.hist, &r->cl.res})
+                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->cl.pts, &r->cl.d2, &r->cl.dist, &r->cl.face, &r->cl.xyz, &r->cl.side, &r->cl.status, &r->cl.part, &r->cl.hist, &r->cl.res, &r->sm.cnt, &r->sm.off, &r->sm.total, &r->sm.xyz, &r->sm.face})
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t e : r->ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->cl.ev)
         if (e) (void)hipEventDestroy(e);
     if (r->cl.h_res) (void)hipHostFree(r->cl.h_res);
+    for (hipEvent_t e : r->sm.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (r->sm.done) (void)hipEventDestroy(r->sm.done);
+    if (r->sm.h_total) (void)hipHostFree(r->sm.h_total);
     if (r->h_small) (void)hipHostFree(r->h_small);
     if (r->s) (void)hipStreamDestroy(r->s);
     delete r;

@@ -1,0 +1,88 @@
+"""A reconstruction against a ground-truth cloud, both directions, through the C ABI (include/immesh_closest.h, include/immesh_nearest.h):
+  accuracy      the ground-truth points to the mesh: immesh_closest_points + immesh_closest_reduce
+  completeness  area-weighted samples of the mesh to the ground-truth cloud: immesh_mesh_sample, immesh_cloud_index_build, immesh_nearest_samples
+                (the samples never leave the device) + immesh_nearest_reduce
+  chamfer       the sum of the two mean distances
+  precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
+                (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
+The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
+evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
+
+    python tools/mesh_eval.py --cloud gt.npy --ply rec_mesh.ply [--tau 0.05] [--max-dist 1.0] [--density 400] [--seed 0] [--out eval.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from immesh_amd import capi  # noqa: E402
+
+
+def read_ply(path):
+    """the layout immesh_save_ply writes -> vtx (n, 3) float32, faces (m, 3) int32"""
+    raw = open(path, "rb").read()
+    head, body = raw.split(b"end_header\n", 1)
+    if b"format binary_little_endian 1.0" not in head or b"property list uchar int vertex_indices" not in head:
+        raise ValueError(f"{path}: not the binary little-endian layout of immesh_save_ply")
+    lines = head.split(b"\n")
+    nv = int([l for l in lines if l.startswith(b"element vertex")][0].split()[-1])
+    nf = int([l for l in lines if l.startswith(b"element face")][0].split()[-1])
+    vtx = np.frombuffer(body[:nv * 12], np.float32).reshape(-1, 3).copy()
+    rec = np.frombuffer(body[nv * 12:nv * 12 + nf * 13], np.uint8).reshape(nf, 13)
+    if nf and not np.all(rec[:, 0] == 3):
+        raise ValueError(f"{path}: a face that is not a triangle")
+    return vtx, rec[:, 1:].copy().view(np.int32).reshape(nf, 3)
+
+
+def _side(st, hist):
+    finite = st.n_points - st.n_not_finite
+    return {"points": st.n_points, "finite": finite, "within_max_dist": st.n_with_face, "mean": st.mean, "rms": st.rms, "max": st.max_dist,
+            "within_tau": int(hist[0]), "share_within_tau": (int(hist[0]) / finite) if finite else 0.0}
+
+
+def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0):
+    """h: a HotPath with a built caster; cloud (n, 3) float32 ground truth -> dict"""
+    cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    h.closest_points(cloud, max_dist, want=())
+    acc = _side(*h.closest_stats(tau, 1))
+    n_samples = h.mesh_sample(density, seed, fetch=False)
+    n_cloud, n_in = h.cloud_index_build(cloud)
+    h.nearest_samples(max_dist, want=())
+    com = _side(*h.nearest_stats(tau, 1))
+    p, r = com["share_within_tau"], acc["share_within_tau"]
+    return {"tau": tau, "max_dist": max_dist, "density": density, "seed": seed, "samples": n_samples, "cloud_points": n_cloud, "cloud_points_indexed": n_in,
+            "accuracy": acc, "completeness": com, "chamfer": acc["mean"] + com["mean"], "precision": p, "recall": r,
+            "f_score": (2.0 * p * r / (p + r)) if p + r > 0 else 0.0}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cloud", required=True, help="ground-truth points, .npy of shape (n, 3) or (n, >= 3)")
+    ap.add_argument("--ply", required=True, help="a mesh written by immesh_save_ply")
+    ap.add_argument("--tau", type=float, default=0.05)
+    ap.add_argument("--max-dist", type=float, default=1.0, help="pairs farther apart count as unmatched (they leave the means, not the shares)")
+    ap.add_argument("--density", type=float, default=400.0, help="samples per unit area of the mesh")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    cloud = np.load(args.cloud)[:, :3]
+    vtx, faces = read_ply(args.ply)
+    h = capi.HotPath(capi.load_hip_library(), capi.avia_config(cap_root_voxels=1 << 12, cap_scan_points=200000, cap_vertices=1 << 18, cap_triangles=1 << 20), "immesh_")
+    try:
+        sizes = h.raycast_build_triangles(vtx, faces)
+        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]})
+    finally:
+        h.close()
+    print(json.dumps(out), flush=True)
+    if args.out:
+        with open(args.out, "w") as fp:
+            json.dump(out, fp, indent=1)
+
+
+if __name__ == "__main__":
+    main()
