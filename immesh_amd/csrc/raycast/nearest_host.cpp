@@ -3,7 +3,6 @@
 // is allocated or launched unless an index is created or a sample is drawn.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <string>
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_closest.h"
@@ -16,21 +15,6 @@ namespace {
 constexpr int64_t CN_MAX_POINTS = (int64_t)1 << RC_INDEX_BITS;
 constexpr int64_t CN_MAX_QUERY = (int64_t)0x7FFFFFFE;
 
-int cn_grow(immesh_cloud_index* x, RcBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return 0;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        x->ctx->err = "cloud_index: hipMalloc(" + std::to_string(want) + " B) failed";
-        return IMMESH_E_NOMEM;
-    }
-    b.bytes = want;
-    return 0;
-}
-
 int cn_check_query(immesh_cloud_index* x, const char* who, double max_dist) {
     immesh_ctx* c = x->ctx;
     if (!x->built) { c->err = std::string(who) + ": no index has been built (immesh_cloud_index_build)"; return IMMESH_E_INVAL; }
@@ -39,30 +23,27 @@ int cn_check_query(immesh_cloud_index* x, const char* who, double max_dist) {
 }
 
 int cn_grow_results(immesh_cloud_index* x, size_t n) {
+    immesh_ctx* c = x->ctx;
+    RcDist& q = x->q;
     int rc;
-    if ((rc = cn_grow(x, x->d2, n * 8))) return rc;
-    if ((rc = cn_grow(x, x->dist, n * 4))) return rc;
-    if ((rc = cn_grow(x, x->index, n * 4))) return rc;
-    if ((rc = cn_grow(x, x->xyz, n * 12))) return rc;
-    return cn_grow(x, x->status, n);
+    if ((rc = rc_grow(c, "cloud_index", q.d2, n * 8))) return rc;
+    if ((rc = rc_grow(c, "cloud_index", q.dist, n * 4))) return rc;
+    if ((rc = rc_grow(c, "cloud_index", q.id, n * 4))) return rc;
+    if ((rc = rc_grow(c, "cloud_index", q.xyz, n * 12))) return rc;
+    return rc_grow(c, "cloud_index", q.status, n);
 }
 
 // behind the traversal launch: the end event, the wait, the copies
 int cn_finish_query(immesh_cloud_index* x, int64_t n_q, double* d2_out, float* dist_out, int32_t* index_out, float* xyz_out) {
     immesh_ctx* c = x->ctx;
-    const size_t n = (size_t)n_q;
     HIPCHK(c, hipEventRecord(x->ev[3], x->s));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(x->s));
     (void)hipEventElapsedTime(&x->ms[1], x->ev[2], x->ev[3]);
-    if (n_q > 0) {
-        if (d2_out) HIPCHK(c, hipMemcpy(d2_out, x->d2.p, n * 8, hipMemcpyDeviceToHost));
-        if (dist_out) HIPCHK(c, hipMemcpy(dist_out, x->dist.p, n * 4, hipMemcpyDeviceToHost));
-        if (index_out) HIPCHK(c, hipMemcpy(index_out, x->index.p, n * 4, hipMemcpyDeviceToHost));
-        if (xyz_out) HIPCHK(c, hipMemcpy(xyz_out, x->xyz.p, n * 12, hipMemcpyDeviceToHost));
-    }
-    x->n_query = n_q;
-    x->have_query = true;
+    const int rc = rc_dist_copy(c, x->q, n_q, d2_out, dist_out, index_out, xyz_out);
+    if (rc) return rc;
+    x->q.n = n_q;
+    x->q.have = true;
     return 0;
 }
 
@@ -88,7 +69,7 @@ immesh_cloud_index* immesh_cloud_index_create(immesh_ctx* ctx) {
     bool ok = hipStreamCreateWithFlags(&x->s, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; i < 6 && ok; i++) ok = hipEventCreate(&x->ev[i]) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&x->h_small, 32) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&x->h_res, sizeof(ClStatsDev)) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&x->q.h_res, sizeof(DqStatsDev)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         ctx->err = "immesh_cloud_index_create: stream / event / pinned allocation failed";
@@ -102,15 +83,10 @@ void immesh_cloud_index_destroy(immesh_cloud_index* x) {
     if (!x) return;
     (void)hipSetDevice(x->ctx->cfg.device);
     if (x->s) (void)hipStreamSynchronize(x->s);
-    for (RcBuf* b : {&x->pts, &x->nodes, &x->flag, &x->off, &x->ids, &x->box, &x->bounds, &x->code_a, &x->code_b, &x->pos_a, &x->pos_b, &x->leaf, &x->temp,
-                     &x->q_pts, &x->d2, &x->dist, &x->index, &x->xyz, &x->status, &x->part, &x->hist, &x->res})
-        if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t e : x->ev)
-        if (e) (void)hipEventDestroy(e);
+    rc_destroy_events(x->ev, 6);
     if (x->h_small) (void)hipHostFree(x->h_small);
-    if (x->h_res) (void)hipHostFree(x->h_res);
     if (x->s) (void)hipStreamDestroy(x->s);
-    delete x;
+    delete x;   // the records release their buffers and pinned words
 }
 
 int immesh_cloud_index_build(immesh_cloud_index* x, const float* xyz, int64_t n_pts) {
@@ -120,57 +96,14 @@ int immesh_cloud_index_build(immesh_cloud_index* x, const float* xyz, int64_t n_
     if (n_pts < 0 || n_pts > CN_MAX_QUERY || (n_pts > 0 && !xyz)) { c->err = "cloud_index_build: bad point array"; return IMMESH_E_INVAL; }
     if (n_pts > CN_MAX_POINTS) { c->err = "cloud_index_build: more than 2^30 points"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
-    hipStream_t s = x->s;
-    x->built = false; x->have_query = false;
+    x->built = false; x->q.have = false;
     int rc;
-    const size_t n = (size_t)n_pts;
-    const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n_pts, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n_pts, 1))) + 256;
-    if ((rc = cn_grow(x, x->pts, n * 12))) return rc;
-    if ((rc = cn_grow(x, x->flag, n * 4))) return rc;
-    if ((rc = cn_grow(x, x->off, n * 4))) return rc;
-    if ((rc = cn_grow(x, x->ids, n * 4))) return rc;
-    if ((rc = cn_grow(x, x->box, n * 24))) return rc;
-    if ((rc = cn_grow(x, x->bounds, 32))) return rc;
-    if ((rc = cn_grow(x, x->temp, temp_bytes))) return rc;
-    if (n_pts > 0) HIPCHK(c, hipMemcpyAsync(x->pts.p, xyz, n * 12, hipMemcpyHostToDevice, s));
-    const float* pts = (const float*)x->pts.p;
-    uint32_t* bounds = (uint32_t*)x->bounds.p;
-    int64_t* d_n_in = (int64_t*)(bounds + 6);
-    HIPCHK(c, hipEventRecord(x->ev[0], s));
-    HIPCHK(c, hipMemsetAsync(bounds, 0xFF, 12, s));
-    HIPCHK(c, hipMemsetAsync(bounds + 3, 0, 20, s));
-    int64_t n_in = 0;
-    if (n_pts > 0) {
-        cn_launch_mark(s, pts, n_pts, (int32_t*)x->flag.p);
-        rd_scan_i32(s, x->temp.p, x->temp.bytes, (const int32_t*)x->flag.p, (int32_t*)x->off.p, n_pts);
-        cn_launch_compact(s, pts, n_pts, (const int32_t*)x->flag.p, (const int32_t*)x->off.p, (int32_t*)x->ids.p, (float*)x->box.p, bounds, d_n_in);
-        HIPCHK(c, hipMemcpyAsync(x->h_small, d_n_in, 8, hipMemcpyDeviceToHost, s));   // the one count the host needs: it sizes the tree
-        HIPCHK(c, hipStreamSynchronize(s));
-        n_in = x->h_small[0];
-    }
-    if (n_in > 0) {
-        if ((rc = cn_grow(x, x->code_a, (size_t)n_in * 8))) return rc;
-        if ((rc = cn_grow(x, x->code_b, (size_t)n_in * 8))) return rc;
-        if ((rc = cn_grow(x, x->pos_a, (size_t)n_in * 4))) return rc;
-        if ((rc = cn_grow(x, x->pos_b, (size_t)n_in * 4))) return rc;
-        if ((rc = cn_grow(x, x->leaf, (size_t)n_in * 4))) return rc;
-        if ((rc = cn_grow(x, x->nodes, (size_t)n_in * sizeof(RcNode)))) return rc;
-        RcNode* nodes = (RcNode*)x->nodes.p;
-        if (n_in == 1) {
-            rc_launch_single(s, (const float*)x->box.p, (const int32_t*)x->ids.p, nodes);
-        } else {
-            rc_launch_codes(s, (const float*)x->box.p, n_in, bounds, (unsigned long long*)x->code_a.p, (int32_t*)x->pos_a.p);
-            sort_pairs_u64(s, x->temp.p, x->temp.bytes, (const unsigned long long*)x->code_a.p, (unsigned long long*)x->code_b.p, (const int32_t*)x->pos_a.p,
-                           (int32_t*)x->pos_b.p, (int)n_in, RC_CODE_BITS);
-            rc_launch_hierarchy(s, (const unsigned long long*)x->code_b.p, (const int32_t*)x->ids.p, (const int32_t*)x->pos_b.p, n_in, nodes, (int32_t*)x->leaf.p);
-            rc_launch_refit(s, (const float*)x->box.p, (const int32_t*)x->pos_b.p, (const int32_t*)x->leaf.p, n_in, nodes);
-        }
-    }
-    HIPCHK(c, hipEventRecord(x->ev[1], s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = rc_grow(c, "cloud_index", x->pts, (size_t)n_pts * 12))) return rc;
+    if (n_pts > 0) HIPCHK(c, hipMemcpyAsync(x->pts.p, xyz, (size_t)n_pts * 12, hipMemcpyHostToDevice, x->s));
+    const RcLeaves src = {(const float*)x->pts.p, n_pts, nullptr};
+    if ((rc = rc_tree_build(c, "cloud_index", x->s, x->ev[0], x->ev[1], x->h_small, x->tree, n_pts, src))) return rc;
     (void)hipEventElapsedTime(&x->ms[0], x->ev[0], x->ev[1]);
-    x->n_pts = n_pts; x->n_in = n_in;
+    x->n_pts = n_pts;
     x->built = true;
     return 0;
 }
@@ -179,7 +112,7 @@ int immesh_cloud_index_sizes(immesh_cloud_index* x, int64_t* n_pts, int64_t* n_i
     if (!x) return IMMESH_E_INVAL;
     if (!x->built) { x->ctx->err = "cloud_index_sizes: no index has been built"; return IMMESH_E_INVAL; }
     if (n_pts) *n_pts = x->n_pts;
-    if (n_in_tree) *n_in_tree = x->n_in;
+    if (n_in_tree) *n_in_tree = x->tree.n_in;
     return 0;
 }
 
@@ -192,24 +125,17 @@ int immesh_nearest_points(immesh_cloud_index* x, const immesh_ray_frame* frame, 
     if ((rc = cn_check_query(x, "nearest_points", max_dist))) return rc;
     if (n_q < 0 || n_q > CN_MAX_QUERY || (n_q > 0 && !pts)) { c->err = "nearest_points: bad point array"; return IMMESH_E_INVAL; }
     RcFrame fr = {};
-    if (frame) {
-        for (int i = 0; i < 9; i++)
-            if (!std::isfinite(frame->rot[i])) { c->err = "nearest_points: frame rotation is not finite"; return IMMESH_E_INVAL; }
-        for (int i = 0; i < 3; i++)
-            if (!std::isfinite(frame->pos[i])) { c->err = "nearest_points: frame position is not finite"; return IMMESH_E_INVAL; }
-        std::memcpy(fr.rot, frame->rot, sizeof(fr.rot));
-        std::memcpy(fr.pos, frame->pos, sizeof(fr.pos));
-    }
+    if (frame && (rc = rc_frame(c, "nearest_points", frame, &fr))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = x->s;
-    x->have_query = false;
+    x->q.have = false;
     const size_t n = (size_t)n_q;
-    if ((rc = cn_grow(x, x->q_pts, n * 12))) return rc;
+    if ((rc = rc_grow(c, "cloud_index", x->q_pts, n * 12))) return rc;
     if ((rc = cn_grow_results(x, n))) return rc;
     if (n_q > 0) HIPCHK(c, hipMemcpyAsync(x->q_pts.p, pts, n * 12, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(x->ev[2], s));
-    cn_launch_nearest(s, fr, frame != nullptr, (const float*)x->q_pts.p, n_q, max_dist * max_dist, (const float*)x->pts.p, (const RcNode*)x->nodes.p, x->n_in,
-                      (double*)x->d2.p, (float*)x->dist.p, (int32_t*)x->index.p, (float*)x->xyz.p, (uint8_t*)x->status.p);
+    cn_launch_nearest(s, fr, frame != nullptr, (const float*)x->q_pts.p, n_q, max_dist * max_dist, (const float*)x->pts.p, (const RcNode*)x->tree.nodes.p, x->tree.n_in,
+                      (double*)x->q.d2.p, (float*)x->q.dist.p, (int32_t*)x->q.id.p, (float*)x->q.xyz.p, (uint8_t*)x->q.status.p);
     return cn_finish_query(x, n_q, d2_out, dist_out, index_out, xyz_out);
 }
 
@@ -224,58 +150,20 @@ int immesh_nearest_samples(immesh_cloud_index* x, immesh_raycaster* r, double ma
     if (!r->sm.have) { c->err = "nearest_samples: no samples since the caster's last build (immesh_mesh_sample)"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = x->s;
-    x->have_query = false;
+    x->q.have = false;
     const int64_t n_q = r->sm.n;
     if ((rc = cn_grow_results(x, (size_t)n_q))) return rc;
     HIPCHK(c, hipStreamWaitEvent(s, r->sm.done, 0));   // the samples are complete before the traversal reads them
     HIPCHK(c, hipEventRecord(x->ev[2], s));
-    cn_launch_nearest_world(s, (const float*)r->sm.xyz.p, n_q, max_dist * max_dist, (const float*)x->pts.p, (const RcNode*)x->nodes.p, x->n_in, (double*)x->d2.p,
-                            (float*)x->dist.p, (int32_t*)x->index.p, (float*)x->xyz.p, (uint8_t*)x->status.p);
+    cn_launch_nearest(s, RcFrame{}, 0, (const float*)r->sm.xyz.p, n_q, max_dist * max_dist, (const float*)x->pts.p, (const RcNode*)x->tree.nodes.p, x->tree.n_in,
+                      (double*)x->q.d2.p, (float*)x->q.dist.p, (int32_t*)x->q.id.p, (float*)x->q.xyz.p, (uint8_t*)x->q.status.p);
     return cn_finish_query(x, n_q, d2_out, dist_out, index_out, xyz_out);
 }
 
 int immesh_nearest_reduce(immesh_cloud_index* x, double bin_width, int32_t n_bins, immesh_closest_stats* stats, int64_t* hist_out) {
     if (!x) return IMMESH_E_INVAL;
-    immesh_ctx* c = x->ctx;
-    if (!(bin_width > 0.0) || !std::isfinite(bin_width)) { c->err = "nearest_stats: need 0 < bin_width, finite"; return IMMESH_E_INVAL; }
-    if (n_bins < 1 || n_bins > (1 << 20)) { c->err = "nearest_stats: n_bins " + std::to_string(n_bins) + " outside [1, 2^20]"; return IMMESH_E_INVAL; }
-    if (!x->have_query) { c->err = "nearest_stats: no nearest-point query has been made on this index"; return IMMESH_E_INVAL; }
-    (void)hipSetDevice(c->cfg.device);
-    hipStream_t s = x->s;
-    int rc;
-    const int64_t blocks = cl_stats_blocks(x->n_query);
-    const size_t hist_bytes = ((size_t)n_bins + 1) * 8;
-    if ((rc = cn_grow(x, x->part, (size_t)blocks * sizeof(ClStatsDev)))) return rc;
-    if ((rc = cn_grow(x, x->hist, hist_bytes))) return rc;
-    if ((rc = cn_grow(x, x->res, sizeof(ClStatsDev)))) return rc;
-    const float bw = (float)bin_width;
-    HIPCHK(c, hipEventRecord(x->ev[4], s));
-    HIPCHK(c, hipMemsetAsync(x->hist.p, 0, hist_bytes, s));
-    cl_launch_stats(s, (const float*)x->dist.p, (const uint8_t*)x->status.p, x->n_query, bw, n_bins, (ClStatsDev*)x->part.p, (unsigned long long*)x->hist.p,
-                    (ClStatsDev*)x->res.p);
-    HIPCHK(c, hipEventRecord(x->ev[5], s));
-    HIPCHK(c, hipMemcpyAsync(x->h_res, x->res.p, sizeof(ClStatsDev), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&x->ms[2], x->ev[4], x->ev[5]);
-    int64_t overflow = 0;
-    HIPCHK(c, hipMemcpy(&overflow, (const char*)x->hist.p + (size_t)n_bins * 8, 8, hipMemcpyDeviceToHost));
-    if (hist_out) HIPCHK(c, hipMemcpy(hist_out, x->hist.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost));
-    if (stats) {
-        const ClStatsDev& d = *x->h_res;
-        stats->n_points = x->n_query;
-        stats->n_with_face = d.n_face;
-        stats->n_not_finite = d.n_not_finite;
-        stats->n_no_face = d.n_no_face;
-        stats->n_overflow = overflow;
-        stats->sum_dist = d.sum;
-        stats->sum_dist2 = d.sum2;
-        stats->mean = d.n_face > 0 ? d.sum / (double)d.n_face : 0.0;
-        stats->rms = d.n_face > 0 ? std::sqrt(d.sum2 / (double)d.n_face) : 0.0;
-        stats->max_dist = d.max_dist;
-        stats->bin_width = bw;
-    }
-    return 0;
+    return rc_dist_reduce(x->ctx, "nearest_stats", "cloud_index", "no nearest-point query has been made on this index", x->s, x->ev[4], x->ev[5], &x->ms[2],
+                          x->q, bin_width, n_bins, stats, hist_out);
 }
 
 int immesh_nearest_last_timing(immesh_cloud_index* x, float ms[3]) {
@@ -297,10 +185,10 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
     q.have = false; q.n = 0;
     if ((rc = ms_events(r))) return rc;
     const int64_t nf = r->n_faces;
-    if ((rc = rc_grow(r, q.cnt, (size_t)nf * 4))) return rc;
-    if ((rc = rc_grow(r, q.off, (size_t)nf * 4))) return rc;
-    if ((rc = rc_grow(r, q.total, 8))) return rc;
-    if ((rc = rc_grow(r, r->temp, rd_scan_temp_bytes(1, 1, std::max<int64_t>(nf, 1)) + 256))) return rc;
+    if ((rc = rc_grow(c, "raycast", q.cnt, (size_t)nf * 4))) return rc;
+    if ((rc = rc_grow(c, "raycast", q.off, (size_t)nf * 4))) return rc;
+    if ((rc = rc_grow(c, "raycast", q.total, 8))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->tree.temp, rd_scan_temp_bytes(1, 1, std::max<int64_t>(nf, 1)) + 256))) return rc;
     HIPCHK(c, hipEventRecord(q.ev[0], s));
     HIPCHK(c, hipMemsetAsync(q.total.p, 0, 8, s));
     ms_launch_count(s, (const float*)r->vtx.p, r->n_vtx, (const int32_t*)r->faces.p, nf, density, seed, (int32_t*)q.cnt.p, (unsigned long long*)q.total.p);
@@ -314,10 +202,10 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
         c->err = "mesh_sample: too many samples (" + std::to_string(total) + " > 2^31 - 2)";
         return IMMESH_E_CAPACITY;
     }
-    if ((rc = rc_grow(r, q.xyz, (size_t)total * 12))) return rc;
-    if ((rc = rc_grow(r, q.face, (size_t)total * 4))) return rc;
+    if ((rc = rc_grow(c, "raycast", q.xyz, (size_t)total * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", q.face, (size_t)total * 4))) return rc;
     HIPCHK(c, hipEventRecord(q.ev[2], s));
-    if (nf > 0) rd_scan_i32(s, r->temp.p, r->temp.bytes, (const int32_t*)q.cnt.p, (int32_t*)q.off.p, nf);
+    if (nf > 0) rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, (const int32_t*)q.cnt.p, (int32_t*)q.off.p, nf);
     ms_launch_emit(s, (const float*)r->vtx.p, (const int32_t*)r->faces.p, nf, seed, (const int32_t*)q.off.p, total, (float*)q.xyz.p, (int32_t*)q.face.p);
     HIPCHK(c, hipEventRecord(q.ev[3], s));
     HIPCHK(c, hipEventRecord(q.done, s));

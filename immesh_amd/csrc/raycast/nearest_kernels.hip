@@ -1,10 +1,7 @@
 // Mesh-to-cloud distances for gfx950 (include/immesh_nearest.h has the exact contract these kernels implement).
-//   build     cn_mark / cn_compact: the finite points of a cloud with their boxes (lo == hi == the point), the bounds of the centres and the count,
-//             in the layout the caster's build launches read (raycast.hpp); codes, sort, Karras' construction and the refit are the caster's own
-//   nearest   one query per lane, a per-lane stack in private memory (depth bound: raycast.hpp; the keys (code, position) are distinct here too), the
-//             child with the smaller box bound L first.  A node is skipped only when L of its own box exceeds r2 or the best D so far; a point's D
-//             is L of its own box bit for bit, and L is monotone under containment, so no point that wins or ties is ever skipped.
-//             The bound kept on the stack is a float rounded DOWN: it never exceeds L.
+//   nearest   one query per lane on the distance walk of raycast_dev.hpp (dq_walk) over the index's hierarchy (a point is a box whose lo == hi;
+//             built by rc_tree_build like the caster's): the leaf is the squared distance to a cloud point, which is the Box bound of the point's
+//             own box bit for bit
 //   sampler   ms_count: k_f of every face and their int64 total (integer atomics, one per workgroup); the offsets are the renderer's device scan;
 //             ms_emit: one lane per sample, which finds its face by binary search in the offsets; sample (f, j) depends on f, j, the seed and the
 //             face alone, so the launch shape cannot show (one lane per face looping over its samples measures the same: DESIGN.md)
@@ -14,72 +11,18 @@
 
 namespace {
 
-inline unsigned cn_grid(int64_t n) { return (unsigned)((n + RC_BLOCK - 1) / RC_BLOCK); }
-
-// floats -> unsigned keys of the same order (as the caster's build keeps its bounds)
-__device__ __forceinline__ uint32_t cn_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// ---- build ------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RC_BLOCK) cn_mark_kernel(const float* __restrict__ xyz, int64_t n_pts, int32_t* __restrict__ flag) {
-    const int64_t i = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
-    if (i >= n_pts) return;
-    flag[i] = (isfinite(xyz[3 * i]) && isfinite(xyz[3 * i + 1]) && isfinite(xyz[3 * i + 2])) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(RC_BLOCK) cn_compact_kernel(const float* __restrict__ xyz, int64_t n_pts, const int32_t* __restrict__ flag,
-                                                              const int32_t* __restrict__ off, int32_t* __restrict__ ids, float* __restrict__ box,
-                                                              uint32_t* bounds, int64_t* n_in) {
-    __shared__ uint32_t s_b[6];
-    if (threadIdx.x < 6) s_b[threadIdx.x] = threadIdx.x < 3 ? 0xFFFFFFFFu : 0u;
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
-    if (i < n_pts && flag[i]) {
-        const int64_t o = off[i];
-        for (int j = 0; j < 3; j++) {
-            const float c = xyz[3 * i + j];
-            box[6 * o + j] = c;
-            box[6 * o + 3 + j] = c;
-            const uint32_t k = cn_key(0.5f * c + 0.5f * c);   // the centre as rc_launch_codes computes it from the box
-            atomicMin(&s_b[j], k);
-            atomicMax(&s_b[3 + j], k);
-        }
-        ids[o] = (int32_t)i;
-    }
-    if (i == n_pts - 1) n_in[0] = (int64_t)off[i] + flag[i];
-    __syncthreads();
-    if (threadIdx.x < 3) { if (s_b[threadIdx.x] != 0xFFFFFFFFu) atomicMin(&bounds[threadIdx.x], s_b[threadIdx.x]); }
-    else if (threadIdx.x < 6) { if (s_b[threadIdx.x] != 0u) atomicMax(&bounds[threadIdx.x], s_b[threadIdx.x]); }
-}
-
 // ---- nearest ----------------------------------------------------------------------------------------------------------------------------
-// the contract's Point rule: false when the query has no neighbour by rule
-template <bool FRAME>
-__device__ __forceinline__ bool cn_point(const RcFrame& fr, const float* __restrict__ pts, int64_t i, double* p) {
-    const float f[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    bool ok = isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2]);
-    const double x[3] = {(double)f[0], (double)f[1], (double)f[2]};
-    for (int k = 0; k < 3; k++) {
-        p[k] = FRAME ? ((fr.rot[3 * k] * x[0] + fr.rot[3 * k + 1] * x[1]) + fr.rot[3 * k + 2] * x[2]) + fr.pos[k] : x[k];
-        ok = ok && fabs(p[k]) < 0x1p128;   // (false for NaN)
+// the walk's leaf: D of a cloud point; the winner's index is all that is kept
+struct CnPointLeaf {
+    const float* __restrict__ cloud;
+    const double* p;
+    __device__ __forceinline__ double dist(int32_t j) const {
+        const float* c = cloud + 3 * (int64_t)j;
+        const double e0 = (double)c[0] - p[0], e1 = (double)c[1] - p[1], e2 = (double)c[2] - p[2];
+        return (e0 * e0 + e1 * e1) + e2 * e2;
     }
-    return ok;
-}
-
-// the contract's Box bound of a float box
-__device__ __forceinline__ double cn_box(const double* p, const float* lo, const float* hi) {
-    double e[3];
-    for (int k = 0; k < 3; k++) e[k] = fmax(fmax((double)lo[k] - p[k], p[k] - (double)hi[k]), 0.0);
-    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-}
-
-__device__ __forceinline__ float cn_round_down(double x) {   // x >= 0: the largest float <= x
-    float f = (float)x;
-    if ((double)f > x) f = __uint_as_float(__float_as_uint(f) - 1u);
-    return f;
-}
+    __device__ __forceinline__ void accept() const {}
+};
 
 template <bool FRAME>
 __global__ void __launch_bounds__(RC_BLOCK) cn_nearest_kernel(RcFrame fr, const float* __restrict__ pts, int64_t n, double r2,
@@ -89,46 +32,11 @@ __global__ void __launch_bounds__(RC_BLOCK) cn_nearest_kernel(RcFrame fr, const 
     const int64_t i = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     if (i >= n) return;
     double p[3];
-    const bool ok = cn_point<FRAME>(fr, pts, i, p);
+    const bool ok = dq_point(fr, FRAME, pts, i, p);
     double best = r2;              // the bound: r2 until a point counts, then the best D
     int32_t best_i = -1;
-    if (ok && n_in > 0) {
-        int32_t stack[RC_STACK];
-        float stack_key[RC_STACK];
-        int sp = 0;
-        int32_t cur = 0;
-        for (;;) {
-            if (cur < 0) {   // a cloud point
-                const int32_t j = ~cur;
-                const float* c = cloud + 3 * (int64_t)j;
-                const double e0 = (double)c[0] - p[0], e1 = (double)c[1] - p[1], e2 = (double)c[2] - p[2];
-                const double D = (e0 * e0 + e1 * e1) + e2 * e2;
-                // a point met twice (the single-point tree) ties with itself and changes nothing
-                if (D < best || (D == best && (best_i < 0 || j < best_i))) { best = D; best_i = j; }
-            } else {
-                const RcNode& nd = nodes[cur];
-                const double l0 = cn_box(p, nd.lo[0], nd.hi[0]), l1 = cn_box(p, nd.lo[1], nd.hi[1]);
-                const bool h0 = !(l0 > best), h1 = !(l1 > best);
-                const int32_t c0 = nd.child[0], c1 = nd.child[1];
-                if (h0 && h1) {
-                    const bool first0 = l0 <= l1;       // the nearer child first: its points prune the other
-                    stack[sp] = first0 ? c1 : c0;
-                    stack_key[sp] = cn_round_down(first0 ? l1 : l0);
-                    sp++;
-                    cur = first0 ? c0 : c1;
-                    continue;
-                }
-                if (h0 || h1) { cur = h0 ? c0 : c1; continue; }
-            }
-            // next entry whose bound has not been overtaken
-            bool found = false;
-            while (sp > 0) {
-                sp--;
-                if (!((double)stack_key[sp] > best)) { cur = stack[sp]; found = true; break; }
-            }
-            if (!found) break;
-        }
-    }
+    CnPointLeaf leaf = {cloud, p};
+    if (ok && n_in > 0) dq_walk(nodes, p, best, best_i, leaf);
     const bool have = best_i >= 0;
     d2_out[i] = have ? best : -1.0;
     dist_out[i] = have ? (float)sqrt(best) : -1.0f;
@@ -226,35 +134,20 @@ __global__ void __launch_bounds__(RC_BLOCK) ms_emit_kernel(const float* __restri
 
 }  // namespace
 
-void cn_launch_mark(hipStream_t s, const float* xyz, int64_t n_pts, int32_t* flag) {
-    if (n_pts > 0) cn_mark_kernel<<<cn_grid(n_pts), RC_BLOCK, 0, s>>>(xyz, n_pts, flag);
-}
-
-void cn_launch_compact(hipStream_t s, const float* xyz, int64_t n_pts, const int32_t* flag, const int32_t* off, int32_t* ids, float* box, uint32_t* bounds,
-                       int64_t* n_in) {
-    if (n_pts > 0) cn_compact_kernel<<<cn_grid(n_pts), RC_BLOCK, 0, s>>>(xyz, n_pts, flag, off, ids, box, bounds, n_in);
-}
-
 void cn_launch_nearest(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n, double r2, const float* cloud, const RcNode* nodes,
                        int64_t n_in, double* d2, float* dist, int32_t* index, float* xyz, uint8_t* status) {
     if (n <= 0) return;
-    if (has_frame) cn_nearest_kernel<true><<<cn_grid(n), RC_BLOCK, 0, s>>>(fr, pts, n, r2, cloud, nodes, n_in, d2, dist, index, xyz, status);
-    else cn_nearest_kernel<false><<<cn_grid(n), RC_BLOCK, 0, s>>>(fr, pts, n, r2, cloud, nodes, n_in, d2, dist, index, xyz, status);
-}
-
-void cn_launch_nearest_world(hipStream_t s, const float* world_pts, int64_t n, double r2, const float* cloud, const RcNode* nodes, int64_t n_in, double* d2,
-                             float* dist, int32_t* index, float* xyz, uint8_t* status) {
-    const RcFrame none = {};
-    if (n > 0) cn_nearest_kernel<false><<<cn_grid(n), RC_BLOCK, 0, s>>>(none, world_pts, n, r2, cloud, nodes, n_in, d2, dist, index, xyz, status);
+    if (has_frame) cn_nearest_kernel<true><<<rc_grid(n), RC_BLOCK, 0, s>>>(fr, pts, n, r2, cloud, nodes, n_in, d2, dist, index, xyz, status);
+    else cn_nearest_kernel<false><<<rc_grid(n), RC_BLOCK, 0, s>>>(fr, pts, n, r2, cloud, nodes, n_in, d2, dist, index, xyz, status);
 }
 
 void ms_launch_count(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, double density, uint64_t seed, int32_t* cnt,
                      unsigned long long* total) {
-    if (n_faces > 0) ms_count_kernel<<<cn_grid(n_faces), RC_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, density, (unsigned long long)seed, cnt, total);
+    if (n_faces > 0) ms_count_kernel<<<rc_grid(n_faces), RC_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, density, (unsigned long long)seed, cnt, total);
 }
 
 void ms_launch_emit(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, uint64_t seed, const int32_t* off, int64_t n_samples, float* xyz,
                     int32_t* face) {
     if (n_samples > 0 && n_faces > 0)
-        ms_emit_kernel<<<cn_grid(n_samples), RC_BLOCK, 0, s>>>(vtx, faces, n_faces, (unsigned long long)seed, off, n_samples, xyz, face);
+        ms_emit_kernel<<<rc_grid(n_samples), RC_BLOCK, 0, s>>>(vtx, faces, n_faces, (unsigned long long)seed, off, n_samples, xyz, face);
 }

@@ -27,32 +27,39 @@ static_assert(sizeof(RcNode) == 64, "RcNode layout");
 
 struct RcFrame { double rot[9], pos[3]; };
 
-// one partial of the closest-point reduction, and its folded result
-struct ClStatsDev {
+// one partial of a distance query's reduction (closest face, nearest cloud point), and its folded result
+struct DqStatsDev {
     double sum, sum2;
     int64_t n_face, n_not_finite, n_no_face;
     float max_dist;
     int32_t pad;
 };
-static_assert(sizeof(ClStatsDev) == 48, "ClStatsDev layout");
-constexpr int CL_LDS_BINS = 1024;
+static_assert(sizeof(DqStatsDev) == 48, "DqStatsDev layout");
+constexpr int DQ_LDS_BINS = 1024;
+
+// the items of a build, one per leaf: the faces of a soup, or (faces == nullptr) the points of a cloud, xyz[3 i]: a point is a box whose lo == hi
+struct RcLeaves {
+    const float* xyz;
+    int64_t n_vtx;
+    const int32_t* faces;
+};
 
 // build -----------------------------------------------------------------------------------------------------------------------------------
-// flag[f] = 1 when face f enters the tree (indices in range, nine finite coordinates)
-void rc_launch_mark(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, int32_t* flag);
-// ids[off[f]] = f for the marked faces, box[6 i] = the float box (lo xyz, hi xyz) of ids[i]; bounds[6] (order-preserving keys, preset to
-// 0xFFFFFFFF x 3, 0 x 3) = min / max over the boxes' centres;  n_in[0] = the number of marked faces
-void rc_launch_compact(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, const int32_t* flag, const int32_t* off, int32_t* ids,
-                       float* box, uint32_t* bounds, int64_t* n_in);
+// flag[i] = 1 when item i enters the tree: a face with its indices in range and nine finite coordinates, a point with three finite floats
+void rc_launch_mark(hipStream_t s, const RcLeaves& src, int64_t n, int32_t* flag);
+// ids[off[i]] = i for the marked items, box[6 j] = the float box (lo xyz, hi xyz) of ids[j]; bounds[6] (order-preserving keys, preset to
+// 0xFFFFFFFF x 3, 0 x 3) = min / max over the boxes' centres;  n_in[0] = the number of marked items
+void rc_launch_compact(hipStream_t s, const RcLeaves& src, int64_t n, const int32_t* flag, const int32_t* off, int32_t* ids, float* box, uint32_t* bounds,
+                       int64_t* n_in);
 // code[i] = the Morton code of box i's centre in the bounds, iota[i] = i (the sort's values)
 void rc_launch_codes(hipStream_t s, const float* box, int64_t n_in, const uint32_t* bounds, unsigned long long* code, int32_t* iota);
 // Karras' construction over the sorted codes (ties broken by position): nodes[0 .. n_in - 2], leaf_parent[i] = (node << 1) | side; sorted leaf i is
-// face ids[pos_sorted[i]].  n_in >= 2.
+// item ids[pos_sorted[i]].  n_in >= 2.
 void rc_launch_hierarchy(hipStream_t s, const unsigned long long* code, const int32_t* ids, const int32_t* pos_sorted, int64_t n_in, RcNode* nodes,
                          int32_t* leaf_parent);
 // bottom-up refit, one lane per leaf, one counter per interior node
 void rc_launch_refit(hipStream_t s, const float* box, const int32_t* pos_sorted, const int32_t* leaf_parent, int64_t n_in, RcNode* nodes);
-// the tree of a single face: node 0 with that face as both children (a face tested twice gives the same fragment twice)
+// the tree of a single item: node 0 with that item as both children (a face tested twice gives the same fragment twice)
 void rc_launch_single(hipStream_t s, const float* box, const int32_t* ids, RcNode* nodes);
 
 // cast: t[i], face[i] per the contract (mode 0 NEAREST, 1 ANY); n_in == 0: every ray misses
@@ -62,22 +69,61 @@ void rc_launch_cast(hipStream_t s, const RcFrame& fr, const float* dirs, const f
 void rc_launch_points(hipStream_t s, const RcFrame& fr, const float* dirs, const float* origins, int64_t n_rays, float res, const float* t, float* pts,
                       float* cells, int32_t* keep);
 
-// ---- the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries --------------------
+// ---- the host records: each releases what it holds when it is destroyed, so a buffer is freed by being a member --------------------------------------
 struct immesh_ctx;
+struct immesh_ray_frame;
+struct immesh_closest_stats;
 struct RcBuf {   // grow-only device buffer
     void* p = nullptr;
     size_t bytes = 0;
+    RcBuf() = default;
+    RcBuf(const RcBuf&) = delete;
+    RcBuf& operator=(const RcBuf&) = delete;
+    ~RcBuf() { if (p) (void)hipFree(p); }
 };
+inline void rc_destroy_events(hipEvent_t* e, int n) {
+    for (int i = 0; i < n; i++)
+        if (e[i]) (void)hipEventDestroy(e[i]);
+}
+// grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with "<who>: hipMalloc(... B) failed" in the context
+int rc_grow(immesh_ctx* c, const char* who, RcBuf& b, size_t bytes);
+// checks a frame (twelve finite values; "<who>: frame rotation / position is not finite") and copies it
+int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr);
+
+// a hierarchy and the scratch of its build: the caster's over faces, the cloud index's over points
+struct RcTree {
+    RcBuf nodes;
+    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;
+    int64_t n_in = 0;                                          // leaves
+};
+// Builds t over the n items of src (already on the device, queued on s): mark, scan, compact, one host round trip for the count that sizes the tree
+// (h_count, pinned), then codes, pair sort, Karras' construction and the refit, or the single-leaf tree.  ev0 / ev1 are recorded around the launches;
+// s is idle on return.
+int rc_tree_build(immesh_ctx* c, const char* who, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int64_t* h_count, RcTree& t, int64_t n, const RcLeaves& src);
+
+// the results of a distance query (closest face, nearest cloud point) and their reduction
+struct RcDist {
+    RcBuf d2, dist, id, xyz, status;                           // the last query
+    RcBuf part, hist, res;                                     // the reduction: per-workgroup partials, histogram, folded result
+    DqStatsDev* h_res = nullptr;                               // pinned; allocated by the owner
+    int64_t n = 0;
+    bool have = false;
+    ~RcDist() { if (h_res) (void)hipHostFree(h_res); }
+};
+// d2, dist, id, xyz of the last query to the host arrays that are not NULL (the stream is idle)
+int rc_dist_copy(immesh_ctx* c, const RcDist& q, int64_t n, double* d2_out, float* dist_out, int32_t* id_out, float* xyz_out);
+// the reduction behind immesh_closest_reduce and immesh_nearest_reduce: `who` prefixes the messages, `grow_who` those of rc_grow, `none` is the text
+// when no query has been made; ev0 / ev1 are recorded around the launches and *ms is their span
+int rc_dist_reduce(immesh_ctx* c, const char* who, const char* grow_who, const char* none, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, float* ms,
+                   RcDist& q, double bin_width, int32_t n_bins, immesh_closest_stats* stats, int64_t* hist_out);
 
 // closest-point queries: allocated at the first query, never before
 struct RcClosest {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // query, reduction: begin / end
-    RcBuf pts, d2, dist, face, xyz, side, status;              // the last query: its points and its results
-    RcBuf part, hist, res;                                     // the reduction: per-workgroup partials, histogram, folded result
-    ClStatsDev* h_res = nullptr;                               // pinned
-    bool have_query = false;
-    int64_t n_pts = 0;
+    RcDist q;                                                  // id: the face
+    RcBuf pts, side;                                           // the last query's points; the side of the face
     float ms[2] = {0.0f, 0.0f};
+    ~RcClosest() { rc_destroy_events(ev, 4); }
 };
 
 // samples of the snapshot (include/immesh_nearest.h): allocated at the first immesh_mesh_sample, never before
@@ -89,19 +135,25 @@ struct RcSample {
     bool have = false;                                         // samples of the current snapshot exist
     int64_t n = 0;
     float ms[2] = {0.0f, 0.0f};
+    ~RcSample() {
+        rc_destroy_events(ev, 4);
+        rc_destroy_events(&done, 1);
+        if (h_total) (void)hipHostFree(h_total);
+    }
 };
 
+// the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
     hipStream_t s = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // build, cast, reinforce: begin / end
     int64_t* h_small = nullptr;   // pinned: [0] faces in the tree, [1] reinforced points
-    RcBuf vtx, faces, nodes;                                                       // the built snapshot
-    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
+    RcBuf vtx, faces;                                                              // the built snapshot
+    RcTree tree;                                                                   // (its temp also serves the reinforce pass and the sampler)
     RcBuf dirs[2], org[2], t[2], face[2];                                          // the last cast of each mode ([0] NEAREST: the reinforce pass reads it)
     RcBuf pts, cells, keep, koff, slot, tab, out, small;                           // reinforce
     bool built = false;
-    int64_t n_vtx = 0, n_faces = 0, n_in = 0;
+    int64_t n_vtx = 0, n_faces = 0;
     // the last NEAREST cast, as the reinforce pass reads it
     bool have_cast = false, have_origins = false;
     int64_t n_rays = 0;
@@ -111,49 +163,38 @@ struct immesh_raycaster {
     RcClosest cl;
     RcSample sm;
 };
-// grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with text in the context
-int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes);
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------
 // status[i]: 0 a face, 1 no face within max_dist, 2 the point is not finite.  has_frame == 0: the points are world coordinates.
-void cl_launch_query(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n_pts, double r2, const float* vtx,
-                     const int32_t* faces, const RcNode* nodes, int64_t n_in, double* d2, float* dist, int32_t* face, float* xyz, int8_t* side, uint8_t* status);
-// part[b] = the partial of workgroup b (cl_stats_blocks(n_pts) of them), hist[0 .. n_bins) += the bins, hist[n_bins] += the overflow (hist zeroed by the
-// caller; up to CL_LDS_BINS bins are counted in LDS first);
+void rc_launch_closest(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n_pts, double r2, const float* vtx,
+                       const int32_t* faces, const RcNode* nodes, int64_t n_in, double* d2, float* dist, int32_t* face, float* xyz, int8_t* side, uint8_t* status);
+// part[b] = the partial of workgroup b (dq_stats_blocks(n_pts) of them), hist[0 .. n_bins) += the bins, hist[n_bins] += the overflow (hist zeroed by the
+// caller; up to DQ_LDS_BINS bins are counted in LDS first);
 // then res[0] = the partials folded in index order
-int64_t cl_stats_blocks(int64_t n_pts);
-void cl_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, int64_t n_pts, float bin_width, int32_t n_bins, ClStatsDev* part,
-                     unsigned long long* hist, ClStatsDev* res);
+int64_t dq_stats_blocks(int64_t n_pts);
+void dq_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, int64_t n_pts, float bin_width, int32_t n_bins, DqStatsDev* part,
+                     unsigned long long* hist, DqStatsDev* res);
 
 // ---- mesh-to-cloud distances (include/immesh_nearest.h): nearest_host.cpp owns the index and the sampler's host side ---------------------------------
-// An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi.  The build runs cn_launch_mark / cn_launch_compact and then
-// the caster's own launches (rc_launch_codes, the pair sort, rc_launch_hierarchy, rc_launch_refit; rc_launch_single for one point), one point per leaf.
+// An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi, built by the same rc_tree_build, one point per leaf.
 struct immesh_cloud_index {
     immesh_ctx* ctx = nullptr;
     hipStream_t s = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // build, query, reduction: begin / end
     int64_t* h_small = nullptr;   // pinned: [0] points in the tree
-    ClStatsDev* h_res = nullptr;  // pinned
-    RcBuf pts, nodes;                                                              // the built cloud
-    RcBuf flag, off, ids, box, bounds, code_a, code_b, pos_a, pos_b, leaf, temp;   // build scratch
-    RcBuf q_pts, d2, dist, index, xyz, status;                                     // the last query: its host-copied points and its results
-    RcBuf part, hist, res;                                                         // the reduction
-    bool built = false, have_query = false;
-    int64_t n_pts = 0, n_in = 0, n_query = 0;
+    RcBuf pts;                                                                     // the built cloud
+    RcTree tree;
+    RcBuf q_pts;                                                                   // the last query's host-copied points
+    RcDist q;                                                                      // id: the cloud point
+    bool built = false;
+    int64_t n_pts = 0;
     float ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
-// flag[i] = 1 when cloud point i enters the tree (three finite floats)
-void cn_launch_mark(hipStream_t s, const float* xyz, int64_t n_pts, int32_t* flag);
-// ids[off[i]] = i for the marked points, box[6 j] = (c, c) of ids[j]; bounds[6] and n_in[0] as rc_launch_compact leaves them
-void cn_launch_compact(hipStream_t s, const float* xyz, int64_t n_pts, const int32_t* flag, const int32_t* off, int32_t* ids, float* box, uint32_t* bounds,
-                       int64_t* n_in);
-// nearest cloud point of every query; status[i] as cl_launch_query writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
-// cl_launch_stats reduces it.  n_in == 0 reads no node.  Two entries: points copied from the host, with an optional frame; a device array of world floats.
+// nearest cloud point of every query; status[i] as rc_launch_closest writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
+// dq_launch_stats reduces it.  n_in == 0 reads no node.  has_frame == 0: pts are world floats (the host's points, or the sampler's on the device).
 void cn_launch_nearest(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n, double r2, const float* cloud, const RcNode* nodes,
                        int64_t n_in, double* d2, float* dist, int32_t* index, float* xyz, uint8_t* status);
-void cn_launch_nearest_world(hipStream_t s, const float* world_pts, int64_t n, double r2, const float* cloud, const RcNode* nodes, int64_t n_in, double* d2,
-                             float* dist, int32_t* index, float* xyz, uint8_t* status);
 // the sampler: cnt[f] = min(k_f, 2^31 - 1), total[0] (zeroed by the caller) += k_f
 void ms_launch_count(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, double density, uint64_t seed, int32_t* cnt,
                      unsigned long long* total);

@@ -8,7 +8,7 @@
 #include "../render/render.hpp"
 #include "raycast.hpp"
 
-int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) {
+int rc_grow(immesh_ctx* c, const char* who, RcBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (b.bytes >= bytes) return 0;
     if (b.p) (void)hipFree(b.p);
@@ -16,10 +16,71 @@ int rc_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) {
     const size_t want = bytes + bytes / 4;
     if (hipMalloc(&b.p, want) != hipSuccess) {
         (void)hipGetLastError();
-        r->ctx->err = "raycast: hipMalloc(" + std::to_string(want) + " B) failed";
+        c->err = std::string(who) + ": hipMalloc(" + std::to_string(want) + " B) failed";
         return IMMESH_E_NOMEM;
     }
     b.bytes = want;
+    return 0;
+}
+
+int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr) {
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(frame->rot[i])) { c->err = std::string(who) + ": frame rotation is not finite"; return IMMESH_E_INVAL; }
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(frame->pos[i])) { c->err = std::string(who) + ": frame position is not finite"; return IMMESH_E_INVAL; }
+    std::memcpy(fr->rot, frame->rot, sizeof(fr->rot));
+    std::memcpy(fr->pos, frame->pos, sizeof(fr->pos));
+    return 0;
+}
+
+int rc_tree_build(immesh_ctx* c, const char* who, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int64_t* h_count, RcTree& t, int64_t n, const RcLeaves& src) {
+    int rc;
+    const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n, 1))) + 256;
+    if ((rc = rc_grow(c, who, t.flag, (size_t)n * 4))) return rc;
+    if ((rc = rc_grow(c, who, t.off, (size_t)n * 4))) return rc;
+    if ((rc = rc_grow(c, who, t.ids, (size_t)n * 4))) return rc;
+    if ((rc = rc_grow(c, who, t.box, (size_t)n * 24))) return rc;
+    if ((rc = rc_grow(c, who, t.bounds, 32))) return rc;
+    if ((rc = rc_grow(c, who, t.temp, temp_bytes))) return rc;
+    int32_t *flag = (int32_t*)t.flag.p, *off = (int32_t*)t.off.p, *ids = (int32_t*)t.ids.p;
+    float* box = (float*)t.box.p;
+    uint32_t* bounds = (uint32_t*)t.bounds.p;
+    int64_t* d_n_in = (int64_t*)(bounds + 6);
+    HIPCHK(c, hipEventRecord(ev0, s));
+    HIPCHK(c, hipMemsetAsync(bounds, 0xFF, 12, s));
+    HIPCHK(c, hipMemsetAsync(bounds + 3, 0, 20, s));
+    int64_t n_in = 0;
+    if (n > 0) {
+        rc_launch_mark(s, src, n, flag);
+        rd_scan_i32(s, t.temp.p, t.temp.bytes, flag, off, n);
+        rc_launch_compact(s, src, n, flag, off, ids, box, bounds, d_n_in);
+        HIPCHK(c, hipMemcpyAsync(h_count, d_n_in, 8, hipMemcpyDeviceToHost, s));   // the one count the host needs: it sizes the tree
+        HIPCHK(c, hipStreamSynchronize(s));
+        n_in = h_count[0];
+    }
+    if (n_in > 0) {
+        if ((rc = rc_grow(c, who, t.code_a, (size_t)n_in * 8))) return rc;
+        if ((rc = rc_grow(c, who, t.code_b, (size_t)n_in * 8))) return rc;
+        if ((rc = rc_grow(c, who, t.pos_a, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(c, who, t.pos_b, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(c, who, t.leaf, (size_t)n_in * 4))) return rc;
+        if ((rc = rc_grow(c, who, t.nodes, (size_t)n_in * sizeof(RcNode)))) return rc;
+        RcNode* nodes = (RcNode*)t.nodes.p;
+        if (n_in == 1) {
+            rc_launch_single(s, box, ids, nodes);
+        } else {
+            unsigned long long *code_a = (unsigned long long*)t.code_a.p, *code_b = (unsigned long long*)t.code_b.p;
+            int32_t *pos_a = (int32_t*)t.pos_a.p, *pos_b = (int32_t*)t.pos_b.p, *leaf = (int32_t*)t.leaf.p;
+            rc_launch_codes(s, box, n_in, bounds, code_a, pos_a);
+            sort_pairs_u64(s, t.temp.p, t.temp.bytes, code_a, code_b, pos_a, pos_b, (int)n_in, RC_CODE_BITS);
+            rc_launch_hierarchy(s, code_b, ids, pos_b, n_in, nodes, leaf);
+            rc_launch_refit(s, box, pos_b, leaf, n_in, nodes);
+        }
+    }
+    HIPCHK(c, hipEventRecord(ev1, s));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    t.n_in = n_in;
     return 0;
 }
 
@@ -44,57 +105,13 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
 
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
-    immesh_ctx* c = r->ctx;
-    hipStream_t s = r->s;
     r->built = false; r->have_cast = false; r->n_points = 0;
     r->sm.have = false;   // samples belong to the snapshot they were drawn from
-    int rc;
-    const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n_faces, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n_faces, 1))) + 256;
-    if ((rc = rc_grow(r, r->flag, (size_t)n_faces * 4))) return rc;
-    if ((rc = rc_grow(r, r->off, (size_t)n_faces * 4))) return rc;
-    if ((rc = rc_grow(r, r->ids, (size_t)n_faces * 4))) return rc;
-    if ((rc = rc_grow(r, r->box, (size_t)n_faces * 24))) return rc;
-    if ((rc = rc_grow(r, r->bounds, 32))) return rc;
-    if ((rc = rc_grow(r, r->temp, temp_bytes))) return rc;
-    const float* vtx = (const float*)r->vtx.p;
-    const int32_t* faces = (const int32_t*)r->faces.p;
-    uint32_t* bounds = (uint32_t*)r->bounds.p;
-    int64_t* d_n_in = (int64_t*)(bounds + 6);
-    HIPCHK(c, hipEventRecord(r->ev[0], s));
-    HIPCHK(c, hipMemsetAsync(bounds, 0xFF, 12, s));
-    HIPCHK(c, hipMemsetAsync(bounds + 3, 0, 20, s));
-    int64_t n_in = 0;
-    if (n_faces > 0) {
-        rc_launch_mark(s, vtx, n_vtx, faces, n_faces, (int32_t*)r->flag.p);
-        rd_scan_i32(s, r->temp.p, r->temp.bytes, (const int32_t*)r->flag.p, (int32_t*)r->off.p, n_faces);
-        rc_launch_compact(s, vtx, faces, n_faces, (const int32_t*)r->flag.p, (const int32_t*)r->off.p, (int32_t*)r->ids.p, (float*)r->box.p, bounds, d_n_in);
-        HIPCHK(c, hipMemcpyAsync(r->h_small, d_n_in, 8, hipMemcpyDeviceToHost, s));   // the one count the host needs: it sizes the tree
-        HIPCHK(c, hipStreamSynchronize(s));
-        n_in = r->h_small[0];
-    }
-    if (n_in > 0) {
-        if ((rc = rc_grow(r, r->code_a, (size_t)n_in * 8))) return rc;
-        if ((rc = rc_grow(r, r->code_b, (size_t)n_in * 8))) return rc;
-        if ((rc = rc_grow(r, r->pos_a, (size_t)n_in * 4))) return rc;
-        if ((rc = rc_grow(r, r->pos_b, (size_t)n_in * 4))) return rc;
-        if ((rc = rc_grow(r, r->leaf, (size_t)n_in * 4))) return rc;
-        if ((rc = rc_grow(r, r->nodes, (size_t)n_in * sizeof(RcNode)))) return rc;
-        RcNode* nodes = (RcNode*)r->nodes.p;
-        if (n_in == 1) {
-            rc_launch_single(s, (const float*)r->box.p, (const int32_t*)r->ids.p, nodes);
-        } else {
-            rc_launch_codes(s, (const float*)r->box.p, n_in, bounds, (unsigned long long*)r->code_a.p, (int32_t*)r->pos_a.p);
-            sort_pairs_u64(s, r->temp.p, r->temp.bytes, (const unsigned long long*)r->code_a.p, (unsigned long long*)r->code_b.p, (const int32_t*)r->pos_a.p,
-                           (int32_t*)r->pos_b.p, (int)n_in, RC_CODE_BITS);
-            rc_launch_hierarchy(s, (const unsigned long long*)r->code_b.p, (const int32_t*)r->ids.p, (const int32_t*)r->pos_b.p, n_in, nodes, (int32_t*)r->leaf.p);
-            rc_launch_refit(s, (const float*)r->box.p, (const int32_t*)r->pos_b.p, (const int32_t*)r->leaf.p, n_in, nodes);
-        }
-    }
-    HIPCHK(c, hipEventRecord(r->ev[1], s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
+    const RcLeaves src = {(const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p};
+    const int rc = rc_tree_build(r->ctx, "raycast", r->s, r->ev[0], r->ev[1], r->h_small, r->tree, n_faces, src);
+    if (rc) return rc;
     (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);
-    r->n_vtx = n_vtx; r->n_faces = n_faces; r->n_in = n_in;
+    r->n_vtx = n_vtx; r->n_faces = n_faces;
     r->built = true;
     return 0;
 }
@@ -134,21 +151,10 @@ void immesh_raycaster_destroy(immesh_raycaster* r) {
     if (!r) return;
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
-    for (RcBuf* b : {&r->vtx, &r->faces, &r->nodes, &r->flag, &r->off, &r->ids, &r->box, &r->bounds, &r->code_a, &r->code_b, &r->pos_a, &r->pos_b, &r->leaf,
-                     &r->temp, &r->dirs[0], &r->org[0], &r->t[0], &r->face[0], &r->dirs[1], &r->org[1], &r->t[1], &r->face[1], &r->pts, &r->cells, &r->keep, &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->cl.pts, &r->cl.d2, &r->cl.dist, &r->cl.face, &r->cl.xyz, &r->cl.side, &r->cl.status, &r->cl.part, &r->cl.hist, &r->cl.res, &r->sm.cnt, &r->sm.off, &r->sm.total, &r->sm.xyz, &r->sm.face})
-        if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : r->cl.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (r->cl.h_res) (void)hipHostFree(r->cl.h_res);
-    for (hipEvent_t e : r->sm.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (r->sm.done) (void)hipEventDestroy(r->sm.done);
-    if (r->sm.h_total) (void)hipHostFree(r->sm.h_total);
+    rc_destroy_events(r->ev, 6);
     if (r->h_small) (void)hipHostFree(r->h_small);
     if (r->s) (void)hipStreamDestroy(r->s);
-    delete r;
+    delete r;   // the records release their buffers, events and pinned words
 }
 
 int immesh_raycast_build_triangles(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
@@ -158,8 +164,8 @@ int immesh_raycast_build_triangles(immesh_raycaster* r, const float* vtx_xyz, in
     if (rc) return rc;
     (void)hipSetDevice(c->cfg.device);
     r->built = false;
-    if ((rc = rc_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
-    if ((rc = rc_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->vtx, (size_t)n_vtx * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->faces, (size_t)n_faces * 12))) return rc;
     if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
     if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
     return rc_build(r, n_vtx, n_faces);
@@ -175,8 +181,8 @@ int immesh_raycast_build_mesh(immesh_raycaster* r, double smooth_factor, int32_t
     const MeshHost& h = c->mesh_host;
     (void)hipSetDevice(c->cfg.device);
     r->built = false;
-    if ((rc = rc_grow(r, r->vtx, (size_t)nv * 12))) return rc;
-    if ((rc = rc_grow(r, r->faces, (size_t)nf * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->vtx, (size_t)nv * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->faces, (size_t)nf * 12))) return rc;
     // the snapshot: the caster's own copies, complete before this call returns (rc_build synchronises), so the next export may overwrite its arrays
     if (nv > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, h.exp_vtx, (size_t)nv * 12, hipMemcpyDeviceToDevice, r->s));
     if (nf > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, h.exp_faces, (size_t)nf * 12, hipMemcpyDeviceToDevice, r->s));
@@ -188,7 +194,7 @@ int immesh_raycast_sizes(immesh_raycaster* r, int64_t* n_vtx, int64_t* n_faces, 
     if (!r->built) { r->ctx->err = "raycast_sizes: no hierarchy has been built"; return IMMESH_E_INVAL; }
     if (n_vtx) *n_vtx = r->n_vtx;
     if (n_faces) *n_faces = r->n_faces;
-    if (n_in_tree) *n_in_tree = r->n_in;
+    if (n_in_tree) *n_in_tree = r->tree.n_in;
     return 0;
 }
 
@@ -201,29 +207,24 @@ int immesh_raycast(immesh_raycaster* r, const immesh_ray_frame* frame, const flo
     if (n_rays < 0 || n_rays > (int64_t)0x7FFFFFFE || (n_rays > 0 && !dirs)) { c->err = "raycast: bad ray arrays"; return IMMESH_E_INVAL; }
     if (mode != IMMESH_RAY_NEAREST && mode != IMMESH_RAY_ANY) { c->err = "raycast: unknown mode " + std::to_string(mode); return IMMESH_E_INVAL; }
     if (!(t_min >= 0.0) || !(t_min < t_max) || !std::isfinite(t_max)) { c->err = "raycast: need 0 <= t_min < t_max, both finite"; return IMMESH_E_INVAL; }
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(frame->rot[i])) { c->err = "raycast: frame rotation is not finite"; return IMMESH_E_INVAL; }
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(frame->pos[i])) { c->err = "raycast: frame position is not finite"; return IMMESH_E_INVAL; }
+    RcFrame fr;
+    int rc = rc_frame(c, "raycast", frame, &fr);
+    if (rc) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
-    int rc;
     const int m = mode == IMMESH_RAY_NEAREST ? 0 : 1;   // an ANY cast leaves the last NEAREST cast's rays and distances where the reinforce pass reads them
     if (m == 0) { r->have_cast = false; r->n_points = 0; }
-    if ((rc = rc_grow(r, r->dirs[m], (size_t)n_rays * 12))) return rc;
-    if (origins && (rc = rc_grow(r, r->org[m], (size_t)n_rays * 12))) return rc;
-    if ((rc = rc_grow(r, r->t[m], (size_t)n_rays * 4))) return rc;
-    if ((rc = rc_grow(r, r->face[m], (size_t)n_rays * 4))) return rc;
-    RcFrame fr;
-    std::memcpy(fr.rot, frame->rot, sizeof(fr.rot));
-    std::memcpy(fr.pos, frame->pos, sizeof(fr.pos));
+    if ((rc = rc_grow(c, "raycast", r->dirs[m], (size_t)n_rays * 12))) return rc;
+    if (origins && (rc = rc_grow(c, "raycast", r->org[m], (size_t)n_rays * 12))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->t[m], (size_t)n_rays * 4))) return rc;
+    if ((rc = rc_grow(c, "raycast", r->face[m], (size_t)n_rays * 4))) return rc;
     if (n_rays > 0) {
         HIPCHK(c, hipMemcpyAsync(r->dirs[m].p, dirs, (size_t)n_rays * 12, hipMemcpyHostToDevice, s));
         if (origins) HIPCHK(c, hipMemcpyAsync(r->org[m].p, origins, (size_t)n_rays * 12, hipMemcpyHostToDevice, s));
     }
     HIPCHK(c, hipEventRecord(r->ev[2], s));
     rc_launch_cast(s, fr, (const float*)r->dirs[m].p, origins ? (const float*)r->org[m].p : nullptr, n_rays, t_min, t_max, mode, (const float*)r->vtx.p,
-                   (const int32_t*)r->faces.p, (const RcNode*)r->nodes.p, r->n_in, (float*)r->t[m].p, (int32_t*)r->face[m].p);
+                   (const int32_t*)r->faces.p, (const RcNode*)r->tree.nodes.p, r->tree.n_in, (float*)r->t[m].p, (int32_t*)r->face[m].p);
     HIPCHK(c, hipEventRecord(r->ev[3], s));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
@@ -246,20 +247,20 @@ int immesh_raycast_points(immesh_raycaster* r, double downsample_res, float* xyz
     r->n_points = 0;
     if (n > 0) {
         int rc;
-        if ((rc = rc_grow(r, r->temp, rd_scan_temp_bytes(1, 1, n) + 256))) return rc;
-        if ((rc = rc_grow(r, r->pts, (size_t)n * 12))) return rc;
-        if ((rc = rc_grow(r, r->keep, (size_t)n * 4))) return rc;
-        if ((rc = rc_grow(r, r->koff, (size_t)n * 4))) return rc;
-        if ((rc = rc_grow(r, r->out, (size_t)n * 12))) return rc;
-        if ((rc = rc_grow(r, r->small, 16))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->tree.temp, rd_scan_temp_bytes(1, 1, n) + 256))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->pts, (size_t)n * 12))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->keep, (size_t)n * 4))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->koff, (size_t)n * 4))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->out, (size_t)n * 12))) return rc;
+        if ((rc = rc_grow(c, "raycast", r->small, 16))) return rc;
         uint32_t mask = 0;
         if (res > 0.0f) {
             uint64_t tab = 1024;
             while (tab < 2 * (uint64_t)n) tab <<= 1;
             mask = (uint32_t)(tab - 1);
-            if ((rc = rc_grow(r, r->cells, (size_t)n * 12))) return rc;
-            if ((rc = rc_grow(r, r->slot, (size_t)n * 4))) return rc;
-            if ((rc = rc_grow(r, r->tab, (size_t)tab * 8))) return rc;
+            if ((rc = rc_grow(c, "raycast", r->cells, (size_t)n * 12))) return rc;
+            if ((rc = rc_grow(c, "raycast", r->slot, (size_t)n * 4))) return rc;
+            if ((rc = rc_grow(c, "raycast", r->tab, (size_t)tab * 8))) return rc;
         }
         const float* t = (const float*)r->t[0].p;
         int32_t* keep = (int32_t*)r->keep.p;
@@ -273,7 +274,7 @@ int immesh_raycast_points(immesh_raycaster* r, double downsample_res, float* xyz
             rd_launch_hash_insert(s, n, t, (const float*)r->cells.p, tab_rep, tab_min, mask, (uint32_t*)r->slot.p);
             rd_launch_hash_keep(s, n, t, tab_min, (const uint32_t*)r->slot.p, keep);
         }
-        rd_scan_i32(s, r->temp.p, r->temp.bytes, keep, (int32_t*)r->koff.p, n);
+        rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, keep, (int32_t*)r->koff.p, n);
         rd_launch_compact(s, n, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
         HIPCHK(c, hipEventRecord(r->ev[5], s));
         HIPCHK(c, hipMemcpyAsync(r->h_small + 1, r->small.p, 8, hipMemcpyDeviceToHost, s));

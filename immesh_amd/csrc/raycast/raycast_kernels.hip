@@ -1,6 +1,6 @@
 // Ray casting at a triangle soup for gfx950 (include/immesh_raycast.h has the exact contract these kernels implement).
-//   build     mark the faces that enter the tree, compact them with their float boxes, reduce the bounds of the box centres (order-preserving
-//             keys, atomicMin / atomicMax), 63-bit Morton codes, rocPRIM's stable radix sort (sort.o; equal codes keep face order), Karras'
+//   build     of the caster's faces and of a cloud index's points alike: mark the items that enter the tree, compact them with their float boxes,
+//             reduce the bounds of the box centres (order-preserving keys, atomicMin / atomicMax), 63-bit Morton codes, rocPRIM's stable radix sort (sort.o; equal codes keep face order), Karras'
 //             construction (one lane per interior node), bottom-up refit (one lane per leaf, the second arrival at a node goes on)
 //   cast      one ray per lane, a per-lane stack in private memory (depth bound: raycast.hpp), the nearer child first; a node is skipped only
 //             by the contract's Box arithmetic on its own box, which can never cull a face that counts
@@ -18,45 +18,52 @@ __device__ __forceinline__ uint32_t rc_key(float v) {
 }
 __device__ __forceinline__ float rc_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
-inline unsigned rc_grid(int64_t n) { return (unsigned)((n + RC_BLOCK - 1) / RC_BLOCK); }
-
 // ---- build ------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RC_BLOCK) rc_mark_kernel(const float* __restrict__ vtx, int64_t n_vtx, const int32_t* __restrict__ faces,
-                                                           int64_t n_faces, int32_t* __restrict__ flag) {
+// SOUP: the items are the faces of src; else the points of the cloud src.xyz
+template <bool SOUP>
+__global__ void __launch_bounds__(RC_BLOCK) rc_mark_kernel(RcLeaves src, int64_t n, int32_t* __restrict__ flag) {
     const int64_t f = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
-    if (f >= n_faces) return;
+    if (f >= n) return;
     bool ok = true;
-    for (int k = 0; k < 3; k++) {
-        const int32_t id = faces[3 * f + k];
-        if (id < 0 || (int64_t)id >= n_vtx) { ok = false; break; }
-        for (int j = 0; j < 3; j++) ok = ok && isfinite(vtx[3 * (int64_t)id + j]);
+    for (int k = 0; k < (SOUP ? 3 : 1); k++) {
+        int64_t id = f;
+        if (SOUP) {
+            id = src.faces[3 * f + k];
+            if (id < 0 || id >= src.n_vtx) { ok = false; break; }
+        }
+        for (int j = 0; j < 3; j++) ok = ok && isfinite(src.xyz[3 * id + j]);
     }
     flag[f] = ok ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(RC_BLOCK) rc_compact_kernel(const float* __restrict__ vtx, const int32_t* __restrict__ faces, int64_t n_faces,
-                                                              const int32_t* __restrict__ flag, const int32_t* __restrict__ off,
+template <bool SOUP>
+__global__ void __launch_bounds__(RC_BLOCK) rc_compact_kernel(RcLeaves src, int64_t n, const int32_t* __restrict__ flag, const int32_t* __restrict__ off,
                                                               int32_t* __restrict__ ids, float* __restrict__ box, uint32_t* bounds, int64_t* n_in) {
     __shared__ uint32_t s_b[6];
     if (threadIdx.x < 6) s_b[threadIdx.x] = threadIdx.x < 3 ? 0xFFFFFFFFu : 0u;
     __syncthreads();
     const int64_t f = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
-    if (f < n_faces && flag[f]) {
+    if (f < n && flag[f]) {
         const int64_t i = off[f];
-        float lo[3], hi[3];
         for (int j = 0; j < 3; j++) {
-            const float a = vtx[3 * (int64_t)faces[3 * f] + j], b = vtx[3 * (int64_t)faces[3 * f + 1] + j], c = vtx[3 * (int64_t)faces[3 * f + 2] + j];
-            lo[j] = fminf(fminf(a, b), c);
-            hi[j] = fmaxf(fmaxf(a, b), c);
-            box[6 * i + j] = lo[j];
-            box[6 * i + 3 + j] = hi[j];
-            const uint32_t k = rc_key(0.5f * lo[j] + 0.5f * hi[j]);   // the centre; halves first, so it cannot overflow
+            float lo, hi;
+            if (SOUP) {
+                const float a = src.xyz[3 * (int64_t)src.faces[3 * f] + j], b = src.xyz[3 * (int64_t)src.faces[3 * f + 1] + j],
+                            c = src.xyz[3 * (int64_t)src.faces[3 * f + 2] + j];
+                lo = fminf(fminf(a, b), c);
+                hi = fmaxf(fmaxf(a, b), c);
+            } else {
+                lo = hi = src.xyz[3 * f + j];
+            }
+            box[6 * i + j] = lo;
+            box[6 * i + 3 + j] = hi;
+            const uint32_t k = rc_key(0.5f * lo + 0.5f * hi);   // the centre, as rc_codes_kernel computes it from the box; halves first, so it cannot overflow
             atomicMin(&s_b[j], k);
             atomicMax(&s_b[3 + j], k);
         }
         ids[i] = (int32_t)f;
     }
-    if (f == n_faces - 1) n_in[0] = (int64_t)off[f] + flag[f];
+    if (f == n - 1) n_in[0] = (int64_t)off[f] + flag[f];
     __syncthreads();
     if (threadIdx.x < 3) { if (s_b[threadIdx.x] != 0xFFFFFFFFu) atomicMin(&bounds[threadIdx.x], s_b[threadIdx.x]); }
     else if (threadIdx.x < 6) { if (s_b[threadIdx.x] != 0u) atomicMax(&bounds[threadIdx.x], s_b[threadIdx.x]); }
@@ -248,15 +255,7 @@ __global__ void __launch_bounds__(RC_BLOCK) rc_cast_kernel(RcFrame fr, const flo
                 const int32_t f = ~cur;
                 float lo[3], hi[3];
                 double A[3][3];
-                for (int k = 0; k < 3; k++) {
-                    const float* p = vtx + 3 * (int64_t)faces[3 * (int64_t)f + k];
-                    for (int j = 0; j < 3; j++) {
-                        const float v = p[j];
-                        lo[j] = k ? fminf(lo[j], v) : v;
-                        hi[j] = k ? fmaxf(hi[j], v) : v;
-                        A[k][j] = (double)v - r.o[j];
-                    }
-                }
+                rc_load_face(vtx, faces, f, r.o, lo, hi, A);
                 double ab[3], bc[3], ca[3], n[3];
                 rc_cross(A[0], A[1], ab);
                 rc_cross(A[1], A[2], bc);
@@ -340,13 +339,17 @@ __global__ void __launch_bounds__(RC_BLOCK) rc_points_kernel(RcFrame fr, const f
 
 }  // namespace
 
-void rc_launch_mark(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, int32_t* flag) {
-    if (n_faces > 0) rc_mark_kernel<<<rc_grid(n_faces), RC_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, flag);
+void rc_launch_mark(hipStream_t s, const RcLeaves& src, int64_t n, int32_t* flag) {
+    if (n <= 0) return;
+    if (src.faces) rc_mark_kernel<true><<<rc_grid(n), RC_BLOCK, 0, s>>>(src, n, flag);
+    else rc_mark_kernel<false><<<rc_grid(n), RC_BLOCK, 0, s>>>(src, n, flag);
 }
 
-void rc_launch_compact(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, const int32_t* flag, const int32_t* off, int32_t* ids,
-                       float* box, uint32_t* bounds, int64_t* n_in) {
-    if (n_faces > 0) rc_compact_kernel<<<rc_grid(n_faces), RC_BLOCK, 0, s>>>(vtx, faces, n_faces, flag, off, ids, box, bounds, n_in);
+void rc_launch_compact(hipStream_t s, const RcLeaves& src, int64_t n, const int32_t* flag, const int32_t* off, int32_t* ids, float* box, uint32_t* bounds,
+                       int64_t* n_in) {
+    if (n <= 0) return;
+    if (src.faces) rc_compact_kernel<true><<<rc_grid(n), RC_BLOCK, 0, s>>>(src, n, flag, off, ids, box, bounds, n_in);
+    else rc_compact_kernel<false><<<rc_grid(n), RC_BLOCK, 0, s>>>(src, n, flag, off, ids, box, bounds, n_in);
 }
 
 void rc_launch_codes(hipStream_t s, const float* box, int64_t n_in, const uint32_t* bounds, unsigned long long* code, int32_t* iota) {

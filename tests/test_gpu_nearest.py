@@ -1,8 +1,8 @@
 """Mesh-to-cloud distances on the device (include/immesh_nearest.h): the cloud index, the traversal, the sampler and the reduction against the
-brute-force numpy restatement of the contract (tests/nearest_checker.py), bit for bit -- sizes at which the build and the query change path, equal
-and clustered codes, exact ties, the max_dist boundary, inputs that are not finite, the cross-check against immesh_closest_points on the cloud as a
-soup of degenerate faces, the sampler on every size, the device-resident path, statistics, the live mesh without side effects,
-determinism, argument errors, scale."""
+brute-force numpy restatement of the contract (tests/nearest_checker.py), bit for bit -- sizes at which the build and the query change path, rebuilds
+of the index and the caster (one shared build) from large to small, equal and clustered codes, exact ties, the max_dist boundary, inputs that are
+not finite, the cross-check against immesh_closest_points on the cloud as a soup of degenerate faces, the sampler on every size, the
+device-resident path, statistics, the live mesh without side effects, determinism, argument errors, scale."""
 import ctypes as C
 
 import numpy as np
@@ -108,6 +108,44 @@ def test_sizes_match_checker(hp, n_cloud):
         assert ref[2][-1] == -1 and ref[2][-2] == -1
         _check(hp, r, p, pts, max_dist, cloud, ref, (n_cloud, max_dist, frame is not None))
     assert hp.nearest_points(np.zeros((0, 3), np.float32), 1.0)["index"].shape == (0,)
+
+
+# ---- one build, two owners ------------------------------------------------------------------------------------------------------------------------
+def test_rebuilds_of_both_owners_through_sizes(hp):
+    """the caster and the cloud index of one context share one build: both rebuilt through a large tree, a single leaf, none, two, several workgroups
+    and one wavefront, in that order, and queried after every rebuild -- a bound, a counter or a scratch buffer left over from the larger tree
+    before, or a leaf count of 1 or 0 on the wrong branch, is a wrong bit here.  The soup of two faces has one with a NaN vertex: one leaf of two"""
+    rng = np.random.default_rng(600)
+    rot, pos = _rand_rot(rng), rng.uniform(-2, 2, 3)
+    for n in (5000, 1, 0, 2, 257, 64):
+        cloud = _cloud(rng, n)
+        vtx, faces = _soup(rng, n, spread=5.0, size=0.4) if n else (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+        if n == 2:
+            vtx[faces[1, 0], 1] = np.nan
+        live = cc._soup(vtx, faces)[0]
+        n_fin = int(np.isfinite(cloud).all(axis=1).sum())
+        assert len(live) == len(rcc._soup(vtx, faces)[0]) and (len(live) < n if n in (5000, 2) else len(live) <= n)
+        assert hp.raycast_build_triangles(vtx, faces) == (len(vtx), n, len(live))
+        assert hp.cloud_index_build(cloud) == (n, n_fin)
+        world = _queries(rng, cloud, 300)
+        for r, p, pts, max_dist in ((None, None, world, 100.0), (rot, pos, _local(world, rot, pos), 2.0)):
+            frame = None if r is None else capi.ray_frame(r, p)
+            ref = cc.closest(r, p, pts, max_dist, vtx, faces)
+            if max_dist == 100.0:                                                    # the checkers first: no comparison of misses alone
+                assert (ref[2] >= 0).any() == (len(live) > 0), n
+            _same(hp.closest_points(pts, max_dist, frame), ref, ("closest", n, max_dist), keys=("d2", "dist", "face", "xyz", "side"))
+            ref = nc.nearest(r, p, pts, max_dist, cloud)
+            assert (ref[2] >= 0).any() == (n_fin > 0), (n, max_dist)
+            _same(hp.nearest_points(pts, max_dist, frame), ref, ("nearest", n, max_dist))
+        dirs = rng.normal(size=(300, 3))
+        if len(live):                                                                # half of the rays at the centroids of faces in the tree
+            aim = vtx[faces[live[rng.integers(len(live), size=150)]]].astype(np.float64).mean(axis=1)
+            dirs[:150] = (aim - pos) @ rot
+        dirs = dirs.astype(np.float32)
+        rt, rf = rcc.cast(rot, pos, dirs, None, 0.0, 200.0, vtx, faces)
+        assert (rf >= 0).any() == (len(live) > 0), n
+        t, f = hp.raycast(capi.ray_frame(rot, pos), dirs, None, 0.0, 200.0)
+        assert np.array_equal(f, rf) and t.tobytes() == rt.tobytes(), (n, int((f != rf).sum()))
 
 
 # ---- stack and build extremes --------------------------------------------------------------------------------------------------------------------
