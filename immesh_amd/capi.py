@@ -173,6 +173,17 @@ class ClosestStats(C.Structure):
                 ("max_dist", C.c_float), ("bin_width", C.c_float)]
 
 
+class TopologyStats(C.Structure):
+    """immesh_topology_stats (include/immesh_topology.h): the counts of the last analysis of the caster's snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_faces", "n_counting", "n_degenerate", "n_vertices_used", "n_edges", "n_boundary", "n_interior", "n_nonmanifold",
+                                         "n_inconsistent", "n_components", "largest_component_faces", "n_boundary_loops", "largest_loop_edges", "euler")]
+
+
+assert C.sizeof(TopologyStats) == 112
+EDGE_BOUNDARY, EDGE_NONMANIFOLD, EDGE_INCONSISTENT = 0, 1, 2
+E_INTERNAL = -8
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -877,6 +888,61 @@ class HotPath:
         ms = (C.c_float * 3)()
         self._check(f(self.cloud_index(), ms), "nearest_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # -- the topology of the caster's snapshot (include/immesh_topology.h) ----------------------------------------------------------------------------
+    def topology_analyse(self):
+        """immesh_topology_analyse on the caster's snapshot -> TopologyStats; the analysis stays on the device for the calls below"""
+        f = self.lib.immesh_topology_analyse; f.argtypes = [C.c_void_p, C.POINTER(TopologyStats)]; f.restype = C.c_int
+        st = TopologyStats()
+        self._check(f(self.raycaster(), C.byref(st)), "topology_analyse")
+        return st
+
+    def topology_faces(self):
+        """the component number of every face (-1: the face does not count) -> (n_faces,) int32"""
+        f = self.lib.immesh_topology_faces; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster(), None), "topology_faces")
+        comp = np.empty(self._raycast_sizes()[1], np.int32)
+        self._check(f(self.raycaster(), _ptr(comp)), "topology_faces")
+        return comp
+
+    def topology_components(self):
+        """the component tables -> dict: first_face, n_faces, n_boundary (n,) int32, box (n, 6) float32 (lo xyz, hi xyz)"""
+        f = self.lib.immesh_topology_components; f.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, None, 0, C.byref(n)), "topology_components")
+        out = {"first_face": np.empty(n.value, np.int32), "n_faces": np.empty(n.value, np.int32), "n_boundary": np.empty(n.value, np.int32),
+               "box": np.empty((n.value, 6), np.float32)}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in ("first_face", "n_faces", "n_boundary", "box")], n.value, C.byref(n)), "topology_components")
+        return out
+
+    def topology_edges(self, kind):
+        """the edges of one kind (EDGE_BOUNDARY, EDGE_NONMANIFOLD, EDGE_INCONSISTENT), ascending -> (uv (n, 2) int32, uses (n,) int32)"""
+        f = self.lib.immesh_topology_edges; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), kind, None, None, 0, C.byref(n)), "topology_edges")
+        uv, uses = np.empty((n.value, 2), np.int32), np.empty(n.value, np.int32)
+        self._check(f(self.raycaster(), kind, _ptr(uv), _ptr(uses), n.value, C.byref(n)), "topology_edges")
+        return uv, uses
+
+    def topology_select(self, min_faces=0, min_diagonal=0.0, keep_largest=0, cap=None):
+        """immesh_topology_select -> (keep (n_faces,) int8, the kept faces (n, 3) int32 in face order); cap: the room given for the kept faces (all by
+        default)"""
+        f = self.lib.immesh_topology_select
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        keep = np.empty(self._raycast_sizes()[1], np.int8)
+        self._check(f(self.raycaster(), min_faces, min_diagonal, keep_largest, _ptr(keep), None, 0, C.byref(n)), "topology_select")
+        cap = n.value if cap is None else cap
+        out = np.empty((max(cap, 0), 3), np.int32)
+        self._check(f(self.raycaster(), min_faces, min_diagonal, keep_largest, _ptr(keep), _ptr(out), cap, C.byref(n)), "topology_select")
+        return keep, out[:n.value]
+
+    def topology_timing(self):
+        """device milliseconds of the last (analysis, select)"""
+        f = self.lib.immesh_topology_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "topology_last_timing")
+        return float(ms[0]), float(ms[1])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

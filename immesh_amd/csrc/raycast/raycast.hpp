@@ -142,6 +142,27 @@ struct RcSample {
     }
 };
 
+// the topology of the snapshot (include/immesh_topology.h; topology/topology_host.cpp): allocated at the first immesh_topology_analyse, never before
+struct RcTopology {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // analyse, select: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters, and [16] / [17] the two words of n_counting
+    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+    RcBuf flag, off, used, parent, vparent, loop_cnt;          // per face / per vertex
+    RcBuf key_a, key_b, val_a, val_b;                          // the half-edges; _b sorted (kept for the edge lists)
+    RcBuf label, root, num, comp;                              // per face
+    RcBuf first, nfaces, nbound, box;                          // per component (sized by the counting faces)
+    RcBuf head, eid, start, pick, poff, uv, uses;              // edge lists
+    RcBuf rank_a, rank_b, iota_a, iota_b, keepc, keep32, keep8, koff, out;   // select
+    bool have = false;                                         // an analysis of the current snapshot exists
+    int64_t n_counting = 0, n_half = 0;
+    int64_t st[14] = {};                                       // immesh_topology_stats, in its order
+    float ms[2] = {0.0f, 0.0f};
+    ~RcTopology() {
+        rc_destroy_events(ev, 4);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -162,6 +183,7 @@ struct immesh_raycaster {
     float ms[3] = {0.0f, 0.0f, 0.0f};
     RcClosest cl;
     RcSample sm;
+    RcTopology tp;
 };
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------

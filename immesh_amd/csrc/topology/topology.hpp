@@ -1,0 +1,72 @@
+// Mesh topology of the caster's snapshot (include/immesh_topology.h): the launches topology_host.cpp sequences (the caster's record of them, RcTopology, is in
+// raycast/raycast.hpp beside its other records).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include "../raycast/raycast.hpp"
+
+// the analysis' device counters (int64 each; zeroed before every analysis)
+enum {
+    TP_N_EDGES = 0, TP_N_BOUNDARY, TP_N_INTERIOR, TP_N_NONMANIFOLD, TP_N_INCONSISTENT, TP_N_VERTICES, TP_N_COMPONENTS, TP_LARGEST_COMPONENT, TP_N_LOOPS,
+    TP_LARGEST_LOOP, TP_ERROR, TP_N_KEPT, TP_COUNTERS = 16
+};
+
+// box keys: rc_compact_kernel's order-preserving keys.  Only finite floats are entered, so the presets stay apart from every key.
+constexpr uint32_t TP_KEY_NONE_LO = 0xFFFFFFFFu, TP_KEY_NONE_HI = 0u;
+inline float tp_unkey_host(uint32_t k, bool lo) {
+    uint32_t u;
+    if (k == (lo ? TP_KEY_NONE_LO : TP_KEY_NONE_HI)) u = lo ? 0x7F800000u : 0xFF800000u;   // no finite float: +inf / -inf
+    else u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+// analyse ---------------------------------------------------------------------------------------------------------------------------------
+// flag[f] = 1 for a counting face (three pairwise different indices in [0, n_vtx)), parent[f] = f, used[v] = 1 for its vertices (used zeroed by the caller)
+void tp_launch_mark(hipStream_t s, const int32_t* faces, int64_t n_faces, int64_t n_vtx, int32_t* flag, int32_t* parent, int32_t* used);
+// vparent[v] = v, loop_cnt[v] = 0, cnt[TP_N_VERTICES] += the used vertices
+void tp_launch_vertices(hipStream_t s, int64_t n_vtx, const int32_t* used, int32_t* vparent, int32_t* loop_cnt, unsigned long long* cnt);
+// counting face f, the off[f]-th: key[3 off[f] + k] = (min << 32) | max of use k, val[...] = 3 f + k
+void tp_launch_emit(hipStream_t s, const int32_t* faces, int64_t n_faces, const int32_t* flag, const int32_t* off, unsigned long long* key, int32_t* val);
+// one lane per sorted half-edge: run heads classify their edge (cnt[TP_N_EDGES .. TP_N_INCONSISTENT], one atomic per wavefront and counter) and
+// join a boundary edge's vertices in vparent; every other lane joins its face to its predecessor's in parent.  cnt[TP_ERROR] != 0: a union ran out
+// of its step bound.
+void tp_launch_classify(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, int32_t* parent,
+                        int32_t* vparent, unsigned long long* cnt);
+// label[f] = the root of f (-1: not counting), root[f] = 1 when f is a root
+void tp_launch_flatten(hipStream_t s, const int32_t* parent, const int32_t* flag, int64_t n_faces, int32_t* label, int32_t* root);
+// the component tables before they are filled, n_bound entries: nfaces = nbound = 0, box keys = 0xFFFFFFFF x 3 (lo), 0 x 3 (hi)
+void tp_launch_preset(hipStream_t s, int64_t n_bound, int32_t* nfaces, int32_t* nbound, uint32_t* box);
+// comp[f] = num[label[f]] (-1: not counting); first[c], nfaces[c], box keys (all preset) of the components; cnt[TP_N_COMPONENTS]
+void tp_launch_components(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, const int32_t* label, const int32_t* root,
+                          const int32_t* num, int32_t* comp, int32_t* first, int32_t* nfaces, uint32_t* box, unsigned long long* cnt);
+// the boundary heads again: nbound[comp] (preset), the loops' edge counts in loop_cnt[root vertex], cnt[TP_N_LOOPS], cnt[TP_LARGEST_LOOP]
+void tp_launch_boundary(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* comp, const int32_t* vparent,
+                        int32_t* nbound, int32_t* loop_cnt, unsigned long long* cnt);
+// cnt[TP_LARGEST_COMPONENT] = the largest nfaces[c]
+void tp_launch_largest(hipStream_t s, const int32_t* root, const int32_t* num, const int32_t* nfaces, int64_t n_faces, unsigned long long* cnt);
+
+// edge lists ------------------------------------------------------------------------------------------------------------------------------
+// head[i] = 1 for a run head of the sorted keys
+void tp_launch_heads(hipStream_t s, const unsigned long long* key, int64_t n_half, int32_t* head);
+// start[e] = the position of edge e's head (e = eid[i], the exclusive prefix sum of head), start[n_edges] = n_half
+void tp_launch_starts(hipStream_t s, const int32_t* head, const int32_t* eid, int64_t n_half, int64_t n_edges, int32_t* start);
+// pick[e] = 1 when edge e is of `kind`
+void tp_launch_pick(hipStream_t s, const int32_t* start, int64_t n_edges, const int32_t* val, const int32_t* faces, int32_t kind, int32_t* pick);
+// the picked edges, in order: uv[2 j], uses[j]
+void tp_launch_edges(hipStream_t s, const int32_t* start, int64_t n_edges, const unsigned long long* key, const int32_t* pick, const int32_t* off,
+                     int32_t* uv, int32_t* uses);
+
+// select ----------------------------------------------------------------------------------------------------------------------------------
+// rank_key[c] = ((2^31 - 1 - nfaces[c]) << 32) | c, iota[c] = c
+void tp_launch_rank_keys(hipStream_t s, const int32_t* nfaces, int64_t n_comp, unsigned long long* rank_key, int32_t* iota);
+// keepc[c] by the Select rule, one lane per rank i: c = sorted[i], the components by rank (nullptr when keep_largest == 0: c = i)
+void tp_launch_decide(hipStream_t s, const int32_t* nfaces, const uint32_t* box, int64_t n_comp, int64_t min_faces, double min_diagonal,
+                      int64_t keep_largest, const int32_t* sorted, int32_t* keepc);
+// keep32[f] / keep8[f] = the face's component is kept
+void tp_launch_mask(hipStream_t s, const int32_t* comp, const int32_t* keepc, int64_t n_faces, int32_t* keep32, int8_t* keep8);
+// faces_out[3 off[f]] = face f for the kept faces; cnt[TP_N_KEPT] = their number
+void tp_launch_compact(hipStream_t s, const int32_t* faces, const int32_t* keep32, const int32_t* off, int64_t n_faces, int32_t* faces_out,
+                       unsigned long long* cnt);

@@ -5,10 +5,16 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
+Two options look at the mesh itself first (include/immesh_topology.h), both off by default:
+  --min-component-faces N   analyse the mesh, keep the components of at least N faces, rebuild the caster from the kept faces, then evaluate: the floating
+                            fragments of noise and moving objects leave the figures
+  --topology                the counts of the mesh that is evaluated (components, boundary edges and loops, non-manifold and inconsistent edges,
+                            Euler characteristic) in the output
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
     python tools/mesh_eval.py --cloud gt.npy --ply rec_mesh.ply [--tau 0.05] [--max-dist 1.0] [--density 400] [--seed 0] [--out eval.json]
+                              [--min-component-faces N] [--topology]
 """
 import argparse
 import json
@@ -60,6 +66,21 @@ def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0):
             "f_score": (2.0 * p * r / (p + r)) if p + r > 0 else 0.0}
 
 
+def drop_fragments(h, vtx, faces, min_component_faces):
+    """h: a HotPath whose caster is built over (vtx, faces) -> the caster rebuilt over the components of at least min_component_faces faces;
+    returns (its sizes, what was dropped)"""
+    st = h.topology_analyse()
+    _, kept = h.topology_select(min_faces=min_component_faces)
+    return h.raycast_build_triangles(vtx, kept), {"min_component_faces": min_component_faces, "faces_before": len(faces), "faces_kept": len(kept),
+                                                  "components_before": st.n_components}
+
+
+def topology(h):
+    """the counts of the built caster's mesh -> dict"""
+    st = h.topology_analyse()
+    return {n: getattr(st, n) for n, _ in capi.TopologyStats._fields_}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cloud", required=True, help="ground-truth points, .npy of shape (n, 3) or (n, >= 3)")
@@ -69,13 +90,21 @@ def main():
     ap.add_argument("--density", type=float, default=400.0, help="samples per unit area of the mesh")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--min-component-faces", type=int, default=0, help="drop the components with fewer faces before evaluating (0: keep everything)")
+    ap.add_argument("--topology", action="store_true", help="add the evaluated mesh's topology counts to the output")
     args = ap.parse_args()
     cloud = np.load(args.cloud)[:, :3]
     vtx, faces = read_ply(args.ply)
     h = capi.HotPath(capi.load_hip_library(), capi.avia_config(cap_root_voxels=1 << 12, cap_scan_points=200000, cap_vertices=1 << 18, cap_triangles=1 << 20), "immesh_")
     try:
         sizes = h.raycast_build_triangles(vtx, faces)
-        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]})
+        extra = {}
+        if args.min_component_faces > 0:
+            sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
+        if args.topology:
+            extra["topology"] = topology(h)
+        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
+                   **extra)
     finally:
         h.close()
     print(json.dumps(out), flush=True)
