@@ -184,6 +184,16 @@ EDGE_BOUNDARY, EDGE_NONMANIFOLD, EDGE_INCONSISTENT = 0, 1, 2
 E_INTERNAL = -8
 
 
+class OrientStats(C.Structure):
+    """immesh_orient_stats (include/immesh_topology.h): the counts of the last orientation of the analysed snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_patches", "n_orientable", "n_nonorientable", "largest_patch_faces", "n_faces_flipped", "n_faces_nonorientable",
+                                         "n_patches_inverted", "n_inconsistent_before", "n_inconsistent_after")]
+
+
+assert C.sizeof(OrientStats) == 72
+ORIENT_FIRST, ORIENT_FEWEST, ORIENT_VIEWPOINT = 0, 1, 2
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -942,6 +952,48 @@ class HotPath:
         f = self.lib.immesh_topology_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "topology_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def topology_orient(self, mode, viewpoint=None):
+        """immesh_topology_orient on the analysed snapshot (ORIENT_FIRST, ORIENT_FEWEST, ORIENT_VIEWPOINT with viewpoint (3,)) -> OrientStats; the
+        orientation stays on the device for the calls below"""
+        f = self.lib.immesh_topology_orient; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(OrientStats)]; f.restype = C.c_int
+        o = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        st = OrientStats()
+        self._check(f(self.raycaster(), mode, _ptr(o), C.byref(st)), "topology_orient")
+        return st
+
+    def topology_orient_faces(self):
+        """-> dict: patch (n_faces,) int32 (-1: the face does not count), flip (n_faces,) int8, faces (n_faces, 3) int32: every face, the flipped ones
+        as (i0, i2, i1)"""
+        f = self.lib.immesh_topology_orient_faces; f.argtypes = [C.c_void_p] + [C.c_void_p] * 3; f.restype = C.c_int
+        self._check(f(self.raycaster(), None, None, None), "topology_orient_faces")
+        nf = self._raycast_sizes()[1]
+        out = {"patch": np.empty(nf, np.int32), "flip": np.empty(nf, np.int8), "faces": np.empty((nf, 3), np.int32)}
+        self._check(f(self.raycaster(), _ptr(out["patch"]), _ptr(out["flip"]), _ptr(out["faces"])), "topology_orient_faces")
+        return out
+
+    def topology_orient_patches(self):
+        """the patch tables -> dict: first_face, n_faces, orientable, n_flipped, n_inconsistent (n_patches,) int32"""
+        f = self.lib.immesh_topology_orient_patches; f.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, None, None, 0, C.byref(n)), "topology_orient_patches")
+        names = ("first_face", "n_faces", "orientable", "n_flipped", "n_inconsistent")
+        out = {k: np.empty(n.value, np.int32) for k in names}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in names], n.value, C.byref(n)), "topology_orient_patches")
+        return out
+
+    def topology_orient_apply(self):
+        """immesh_topology_orient_apply: the oriented faces become the caster's, on the device; the analysis and the orientation are discarded as by
+        a build"""
+        f = self.lib.immesh_topology_orient_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "topology_orient_apply")
+
+    def topology_orient_timing(self):
+        """device milliseconds of the last (orient, apply)"""
+        f = self.lib.immesh_topology_orient_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "topology_orient_last_timing")
         return float(ms[0]), float(ms[1])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------

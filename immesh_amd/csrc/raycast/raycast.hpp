@@ -163,6 +163,25 @@ struct RcTopology {
     }
 };
 
+// the orientation of the snapshot's manifold patches (include/immesh_topology.h; topology/orient_host.cpp): allocated at the first
+// immesh_topology_orient, never before.  It reads the analysis' flag and sorted half-edges in RcTopology.
+struct RcOrient {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // orient, apply: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
+    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+    RcBuf cover;                                               // the double cover's parents: node 2 f + s is face f with flip s
+    RcBuf label, base, root, num, patch, flip, out;            // per face (base, flip: int8; out: the oriented faces)
+    RcBuf tab;                                                 // per patch, OT_TABLES int32 arrays of n_counting entries each
+    bool have = false;                                         // an orientation of the current analysis exists
+    int64_t n_bound = 0;                                       // the tables' stride: the analysis' counting faces
+    int64_t st[9] = {};                                        // immesh_orient_stats, in its order
+    float ms[2] = {0.0f, 0.0f};
+    ~RcOrient() {
+        rc_destroy_events(ev, 4);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -184,6 +203,7 @@ struct immesh_raycaster {
     RcClosest cl;
     RcSample sm;
     RcTopology tp;
+    RcOrient ot;
 };
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------

@@ -59,6 +59,37 @@ void tp_launch_pick(hipStream_t s, const int32_t* start, int64_t n_edges, const 
 void tp_launch_edges(hipStream_t s, const int32_t* start, int64_t n_edges, const unsigned long long* key, const int32_t* pick, const int32_t* off,
                      int32_t* uv, int32_t* uses);
 
+// orient (orient_kernels.hip) -------------------------------------------------------------------------------------------------------------
+// the orientation's device counters (int64 each; zeroed before every orientation)
+enum {
+    OT_N_PATCHES = 0, OT_N_ORIENTABLE, OT_N_NONORIENTABLE, OT_LARGEST_PATCH, OT_N_FLIPPED, OT_N_FACES_NONORIENTABLE, OT_N_INVERTED, OT_INCONSISTENT_AFTER,
+    OT_ERROR, OT_COUNTERS = 16
+};
+// the per-patch tables: int32 arrays of n_bound entries each in one buffer (zeroed before every orientation), tab + k * n_bound.  The first five are
+// what immesh_topology_orient_patches returns; the others feed the decision.
+enum { OT_FIRST = 0, OT_NFACES, OT_ORIENTABLE, OT_NFLIPPED, OT_NINCONSISTENT, OT_NBASE1, OT_VOTE_PLUS, OT_VOTE_MINUS, OT_INVERT, OT_TABLES };
+// cover[i] = i for the 2 n_faces nodes of the double cover
+void ot_launch_init(hipStream_t s, int64_t n_nodes, int32_t* cover);
+// one lane per sorted half-edge: the head of a run of exactly two, users f and g, d = both uses have one direction, joins 2 f with 2 g + d and
+// 2 f + 1 with 2 g + 1 - d.  cnt[OT_ERROR] != 0: a union ran out of its step bound.
+void ot_launch_link(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, int32_t* cover,
+                    unsigned long long* cnt);
+// r = the root of 2 f: label[f] = r >> 1 (-1: not counting); base[f] = 2 for a face of a non-orientable patch (2 f and 2 f + 1 have one root), else
+// r & 1; root[f] = 1 when f is its patch's label
+void ot_launch_flatten(hipStream_t s, const int32_t* cover, const int32_t* flag, int64_t n_faces, int32_t* label, int8_t* base, int32_t* root);
+// patch[f] = num[label[f]] (-1); the tables OT_FIRST, OT_ORIENTABLE, OT_NFACES, OT_NBASE1 and, in mode 2, the votes about the viewpoint o;
+// cnt[OT_N_PATCHES]
+void ot_launch_patches(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, const int32_t* label, const int8_t* base, const int32_t* root,
+                       const int32_t* num, int32_t mode, const double* o, int32_t* patch, int32_t* tab, int64_t n_bound, unsigned long long* cnt);
+// the heads of runs of two again, now that the patches are numbered: OT_NINCONSISTENT
+void ot_launch_inconsistent(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, const int32_t* patch,
+                            int32_t* tab, int64_t n_bound);
+// one lane per patch, n_patches read from cnt[OT_N_PATCHES] on the device: OT_INVERT and OT_NFLIPPED by the mode, and the counters of the stats
+void ot_launch_decide(hipStream_t s, int64_t n_bound, int32_t mode, int32_t* tab, unsigned long long* cnt);
+// flip[f] and faces_out[3 f]: (i0, i2, i1) when flipped
+void ot_launch_flip(hipStream_t s, const int32_t* faces, int64_t n_faces, const int32_t* patch, const int8_t* base, const int32_t* tab, int64_t n_bound,
+                    int8_t* flip, int32_t* faces_out);
+
 // select ----------------------------------------------------------------------------------------------------------------------------------
 // rank_key[c] = ((2^31 - 1 - nfaces[c]) << 32) | c, iota[c] = c
 void tp_launch_rank_keys(hipStream_t s, const int32_t* nfaces, int64_t n_comp, unsigned long long* rank_key, int32_t* iota);

@@ -15,64 +15,15 @@
 //   boundary   the boundary heads once more, now that the components are numbered: boundary edges per component, edges per loop
 // All of it integers and min / max: the results do not depend on the order of anything.
 #include "topology.hpp"
+#include "topology_dev.hpp"   // the union-find, the ballot counts and the wavefront folds: the orientation's kernels use them too
 
 namespace {
-
-constexpr int TP_BLOCK = 256;
-constexpr int TP_FOLD_ROUNDS = 4;   // components folded per wavefront before the lanes left over send their own atomics
-inline unsigned tp_grid(int64_t n) { return (unsigned)((n + TP_BLOCK - 1) / TP_BLOCK); }
 
 __device__ __forceinline__ uint32_t tp_key(float v) {
     const uint32_t u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float tp_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-// one atomic per wavefront: the lanes with `pred` counted by a ballot (every lane of the wavefront calls this)
-__device__ __forceinline__ void tp_count(bool pred, unsigned long long* word) {
-    const unsigned long long m = __ballot(pred);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(word, (unsigned long long)__popcll(m));
-}
-
-// ---- union-find ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t tp_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x as this lane sees it, halving the path on the way (the grandparent is an ancestor of x and stays one: hooks happen at roots only);
-// -1 when the steps ran out
-__device__ __forceinline__ int32_t tp_find(int32_t* parent, int32_t x, int64_t& steps) {
-    int32_t p = tp_load(parent + x);
-    while (p != x) {
-        const int32_t g = tp_load(parent + p);
-        if (g != p) atomicMin(parent + x, g);
-        x = p;
-        p = g;
-        if (--steps < 0) return -1;
-    }
-    return x;
-}
-
-// false when the bound was hit
-__device__ __forceinline__ bool tp_union(int32_t* parent, int32_t a, int32_t b) {
-    int64_t steps = 2 * ((int64_t)a + (int64_t)b + 2);
-    for (;;) {
-        a = tp_find(parent, a, steps);
-        b = tp_find(parent, b, steps);
-        if (a < 0 || b < 0) return false;
-        if (a == b) return true;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicCAS(parent + a, a, b);     // the larger root under the smaller
-        if (old == a) return true;
-        a = old;                                             // a was hooked meanwhile, under old < a: go on from there
-        if (--steps < 0) return false;
-    }
-}
-
-// forward: i_k < i_(k + 1 mod 3) of half-edge h = 3 f + k
-__device__ __forceinline__ bool tp_forward(const int32_t* __restrict__ faces, int32_t h) {
-    const int64_t f = h / 3;
-    const int k = h - 3 * (int32_t)f;
-    return faces[3 * f + k] < faces[3 * f + (k == 2 ? 0 : k + 1)];
-}
 
 // ---- analyse ------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TP_BLOCK) tp_mark_kernel(const int32_t* __restrict__ faces, int64_t n_faces, int64_t n_vtx, int32_t* __restrict__ flag,
@@ -154,15 +105,6 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_preset_kernel(int64_t n_bound, in
     nfaces[c] = 0;
     nbound[c] = 0;
     for (int j = 0; j < 3; j++) { box[6 * c + j] = TP_KEY_NONE_LO; box[6 * c + 3 + j] = TP_KEY_NONE_HI; }
-}
-
-__device__ __forceinline__ uint32_t tp_wave_min(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t tp_wave_max(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
-    return v;
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) tp_components_kernel(const float* __restrict__ vtx, const int32_t* __restrict__ faces, int64_t n_faces,

@@ -48,6 +48,42 @@
  * snapshot before any fetch or select -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the caster discards the analysis.
  * A caster with zero faces analyses to all zeros; that is not an error.
  * IMMESH_E_INTERNAL: a union did not finish within its proven bound of steps (a defect of the library, never of the input); the analysis is void.
+ *
+ * ---- Orientation (exact: integers, and per face the sign of one double expression; as order-free as the above) --------------------------------
+ * immesh_topology_orient gives every manifold patch of the analysed snapshot one consistent winding; nothing reaches the caster before _apply.
+ *   Patch:   two counting faces are patch-adjacent when they are the two users of an edge with uses == 2.  Edges with one use, or with three and
+ *            more, join nothing: across a fan there is no "other side" to agree with.  Patches are the classes of the transitive closure (finer than
+ *            the components).  A patch's LABEL is its smallest face index; patches are numbered 0 .. n_patches - 1 by ascending label, and
+ *            patch_out[f] is that number (-1 for a face that does not count).
+ *   Relation: the two users of such an edge AGREE when their uses have opposite directions (the edge is not inconsistent), else they DISAGREE.
+ *   Orientable: a patch is orientable when a map base: its faces -> {0, 1} exists with base[label] = 0 and base[f] xor base[g] = disagree(f, g)
+ *            for every patch-adjacent pair; the map is then unique.  Otherwise the patch is non-orientable (a Moebius band, a Klein bottle): its
+ *            faces are never flipped, in any mode, and the stats and the tables report it.
+ *   Mode:    decides per orientable patch whether the whole patch is inverted; then flip = base xor 1, else flip = base.
+ *            IMMESH_ORIENT_FIRST     never: the label face keeps its winding.
+ *            IMMESH_ORIENT_FEWEST    inverted when 2 #{base = 1} > n_faces: the fewest faces change; a tie keeps FIRST.
+ *            IMMESH_ORIENT_VIEWPOINT a vote of the patch's faces about a viewpoint o (three doubles).  Per face, with its vertices widened to double,
+ *                      a, b, c = v - o;  t = dot(cross(b - a, c - a), -a), cross and dot exactly as in immesh_raycast.h (IEEE double, in the order
+ *                      written, no fused multiply-add);  s = +1 when t > 0, -1 when t < 0, else 0 -- also for a NaN t, for a face with a vertex
+ *                      that is not finite, and for a face of zero area: the side rule of immesh_closest_points with p = o.  The face votes s when base = 0
+ *                      and -s when base = 1 (its sign once wound like the label face).  The patch is inverted when strictly more faces vote -1
+ *                      than +1; a tie keeps FIRST.  Afterwards the majority of a patch's faces show their front to the viewpoint.
+ *   Per face: flip_out[f] = the final flip (0 for a face that does not count and for the faces of a non-orientable patch);  faces_out[f] = face f as
+ *            (i0, i2, i1) when flipped, else unchanged: all n_faces faces in face order, the faces that do not count copied.
+ *   Per patch: first_face (the label), n_faces, orientable (0 / 1), n_flipped (the final flips; 0 when non-orientable), n_inconsistent (the
+ *            inconsistent edges between two of its faces, before orienting).
+ *   Stats:   n_patches, n_orientable, n_nonorientable, largest_patch_faces, n_faces_flipped, n_faces_nonorientable, n_patches_inverted,
+ *            n_inconsistent_before (the analysis' count), n_inconsistent_after (the sum of n_inconsistent over the non-orientable patches: 0 exactly
+ *            when every patch is orientable; an analysis of faces_out counts exactly this many and is otherwise unchanged).
+ *   Apply:   writes faces_out over the caster's face buffer on the device.  Afterwards the caster behaves in every call as one freshly built from the
+ *            same vertices and faces_out by immesh_raycast_build_triangles: equal answers bit for bit, and everything a build discards is discarded
+ *            (the last cast, the samples, the analysis, the orientation).  The hierarchy stays: boxes do not depend on winding.  A ray cast is
+ *            bit-identical before and after.  side_out of immesh_closest_points negates exactly on a flipped winner; its closest point is the
+ *            Face rule on (a, c, b), so d2 may differ in its last bits, and a point as near to two faces may change its winner.
+ * Validated before any launch: an analysis of the current snapshot (the orientation reads its sorted half-edges); mode one of the three; with
+ * VIEWPOINT a viewpoint of three finite doubles below 2^128 in magnitude; cap >= 0; an orientation of the current analysis before any fetch or apply
+ * -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the caster or a new analysis discards the orientation.  Zero faces orient
+ * to all zeros; that is not an error.  IMMESH_E_INTERNAL as above; the orientation is void.
  */
 #ifndef IMMESH_TOPOLOGY_H
 #define IMMESH_TOPOLOGY_H
@@ -97,6 +133,37 @@ int immesh_topology_select(immesh_raycaster* rc, int64_t min_faces, double min_d
 /* Device time in milliseconds from HIP events on the caster's stream: [0] the last analysis (every launch, and the one read-back of the count of
  * counting faces between them)  [1] the last select.  Copies of the results to the host are not included. */
 int immesh_topology_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] analyse  [1] select */
+
+#define IMMESH_ORIENT_FIRST 0
+#define IMMESH_ORIENT_FEWEST 1
+#define IMMESH_ORIENT_VIEWPOINT 2
+
+typedef struct immesh_orient_stats {
+    int64_t n_patches;
+    int64_t n_orientable;
+    int64_t n_nonorientable;
+    int64_t largest_patch_faces;
+    int64_t n_faces_flipped;
+    int64_t n_faces_nonorientable;
+    int64_t n_patches_inverted;
+    int64_t n_inconsistent_before;    /* the analysis' n_inconsistent */
+    int64_t n_inconsistent_after;     /* what an analysis of faces_out counts */
+} immesh_orient_stats;
+
+/* Orient the analysed snapshot by the Orientation rule; viewpoint is read with IMMESH_ORIENT_VIEWPOINT only (NULL otherwise); stats may be NULL.
+ * Nothing is allocated or launched for the orientation before the first call; the buffers are grow-only.  The result stays on the device for the
+ * calls below until the caster is rebuilt, analysed again or _apply has run.  No read-back lies between its launches. */
+int immesh_topology_orient(immesh_raycaster* rc, int32_t mode, const double viewpoint[3], immesh_orient_stats* stats);
+/* patch_out n_faces int32, flip_out n_faces int8, faces_out 3 n_faces int32; each may be NULL. */
+int immesh_topology_orient_faces(immesh_raycaster* rc, int32_t* patch_out, int8_t* flip_out, int32_t* faces_out);
+/* The patch tables, n_patches entries each.  Every pointer may be NULL; n_out gets n_patches.  With any array given, cap < n_patches is
+ * IMMESH_E_CAPACITY (n_out is still set). */
+int immesh_topology_orient_patches(immesh_raycaster* rc, int32_t* first_face, int32_t* n_faces, int32_t* orientable, int32_t* n_flipped,
+                                   int32_t* n_inconsistent, int64_t cap, int64_t* n_out);
+/* The Apply rule: one copy on the device, no host round trip. */
+int immesh_topology_orient_apply(immesh_raycaster* rc);
+/* Device time in milliseconds from HIP events on the caster's stream: [0] the last orient (every launch)  [1] the last apply. */
+int immesh_topology_orient_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] orient  [1] apply */
 
 #ifdef __cplusplus
 }

@@ -5,16 +5,21 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
-Two options look at the mesh itself first (include/immesh_topology.h), both off by default:
+Three options look at the mesh itself first (include/immesh_topology.h), all off by default:
   --min-component-faces N   analyse the mesh, keep the components of at least N faces, rebuild the caster from the kept faces, then evaluate: the floating
                             fragments of noise and moving objects leave the figures
   --topology                the counts of the mesh that is evaluated (components, boundary edges and loops, non-manifold and inconsistent edges,
                             Euler characteristic) in the output
+  --orient first|fewest|viewpoint [--viewpoint X Y Z]
+                            after the fragment filter and before everything else: analyse the mesh, give every manifold patch one winding
+                            (immesh_topology_orient), write it over the caster's faces on the device (immesh_topology_orient_apply).  The output gains
+                            an `orientation` block with the orientation's counts and a `signed` block from the accuracy query's dist and side: the
+                            shares of the ground-truth points in front of, behind and in the plane of their closest face, and the signed mean
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
     python tools/mesh_eval.py --cloud gt.npy --ply rec_mesh.ply [--tau 0.05] [--max-dist 1.0] [--density 400] [--seed 0] [--out eval.json]
-                              [--min-component-faces N] [--topology]
+                              [--min-component-faces N] [--topology] [--orient MODE [--viewpoint X Y Z]]
 """
 import argparse
 import json
@@ -51,10 +56,22 @@ def _side(st, hist):
             "within_tau": int(hist[0]), "share_within_tau": (int(hist[0]) / finite) if finite else 0.0}
 
 
-def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0):
-    """h: a HotPath with a built caster; cloud (n, 3) float32 ground truth -> dict"""
+def _signed(dist, side):
+    """the accuracy query by the side of the closest face -> dict; the shares are over the points with a face within max_dist"""
+    has = dist >= 0
+    n = int(has.sum())
+    front, behind, in_plane = (int((side[has] == k).sum()) for k in (1, -1, 0))
+    mean = float((dist[has].astype(np.float64) * side[has]).sum() / n) if n else 0.0
+    return {"points_with_face": n, "front": front, "behind": behind, "in_plane": in_plane, "share_front": front / n if n else 0.0,
+            "share_behind": behind / n if n else 0.0, "share_in_plane": in_plane / n if n else 0.0, "signed_mean": mean}
+
+
+def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0, signed=False):
+    """h: a HotPath with a built caster; cloud (n, 3) float32 ground truth -> dict; signed: add the `signed` block (it means something once the mesh
+    has been oriented)"""
     cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-    h.closest_points(cloud, max_dist, want=())
+    got = h.closest_points(cloud, max_dist, want=("dist", "side") if signed else ())
+    extra = {"signed": _signed(got["dist"], got["side"])} if signed else {}
     acc = _side(*h.closest_stats(tau, 1))
     n_samples = h.mesh_sample(density, seed, fetch=False)
     n_cloud, n_in = h.cloud_index_build(cloud)
@@ -63,7 +80,7 @@ def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0):
     p, r = com["share_within_tau"], acc["share_within_tau"]
     return {"tau": tau, "max_dist": max_dist, "density": density, "seed": seed, "samples": n_samples, "cloud_points": n_cloud, "cloud_points_indexed": n_in,
             "accuracy": acc, "completeness": com, "chamfer": acc["mean"] + com["mean"], "precision": p, "recall": r,
-            "f_score": (2.0 * p * r / (p + r)) if p + r > 0 else 0.0}
+            "f_score": (2.0 * p * r / (p + r)) if p + r > 0 else 0.0, **extra}
 
 
 def drop_fragments(h, vtx, faces, min_component_faces):
@@ -73,6 +90,20 @@ def drop_fragments(h, vtx, faces, min_component_faces):
     _, kept = h.topology_select(min_faces=min_component_faces)
     return h.raycast_build_triangles(vtx, kept), {"min_component_faces": min_component_faces, "faces_before": len(faces), "faces_kept": len(kept),
                                                   "components_before": st.n_components}
+
+
+ORIENT_MODES = {"first": capi.ORIENT_FIRST, "fewest": capi.ORIENT_FEWEST, "viewpoint": capi.ORIENT_VIEWPOINT}
+
+
+def orient(h, mode, viewpoint=None):
+    """h: a HotPath with a built caster -> its faces oriented on the device (analyse, orient, apply); returns the orientation's counts"""
+    h.topology_analyse()
+    st = h.topology_orient(ORIENT_MODES[mode], viewpoint if mode == "viewpoint" else None)
+    h.topology_orient_apply()
+    out = {"mode": mode, **{n: getattr(st, n) for n, _ in capi.OrientStats._fields_}}
+    if mode == "viewpoint":
+        out["viewpoint"] = [float(x) for x in viewpoint]
+    return out
 
 
 def topology(h):
@@ -92,7 +123,11 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--min-component-faces", type=int, default=0, help="drop the components with fewer faces before evaluating (0: keep everything)")
     ap.add_argument("--topology", action="store_true", help="add the evaluated mesh's topology counts to the output")
+    ap.add_argument("--orient", choices=sorted(ORIENT_MODES), default=None, help="orient every manifold patch consistently before evaluating")
+    ap.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --orient viewpoint: the point the faces should face")
     args = ap.parse_args()
+    if (args.orient == "viewpoint") != (args.viewpoint is not None):
+        ap.error("--viewpoint X Y Z goes with --orient viewpoint, and only with it")
     cloud = np.load(args.cloud)[:, :3]
     vtx, faces = read_ply(args.ply)
     h = capi.HotPath(capi.load_hip_library(), capi.avia_config(cap_root_voxels=1 << 12, cap_scan_points=200000, cap_vertices=1 << 18, cap_triangles=1 << 20), "immesh_")
@@ -101,9 +136,11 @@ def main():
         extra = {}
         if args.min_component_faces > 0:
             sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
+        if args.orient:
+            extra["orientation"] = orient(h, args.orient, args.viewpoint)
         if args.topology:
             extra["topology"] = topology(h)
-        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
+        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
                    **extra)
     finally:
         h.close()
