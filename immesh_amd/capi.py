@@ -194,6 +194,16 @@ assert C.sizeof(OrientStats) == 72
 ORIENT_FIRST, ORIENT_FEWEST, ORIENT_VIEWPOINT = 0, 1, 2
 
 
+class HolesStats(C.Structure):
+    """immesh_holes_stats (include/immesh_topology.h): the counts of the last holes pass over the analysed snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_loops", "n_simple", "n_nonsimple", "n_outline", "n_too_long", "n_too_wide", "n_blocked", "n_filled",
+                                         "n_new_faces", "n_edges_closed", "largest_simple_loop_edges", "n_cycle_vertices")]
+
+
+assert C.sizeof(HolesStats) == 96
+HOLE_FILLED, HOLE_NONSIMPLE, HOLE_OUTLINE, HOLE_TOO_LONG, HOLE_TOO_WIDE, HOLE_BLOCKED = 0, 1, 2, 3, 4, 5
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -994,6 +1004,57 @@ class HotPath:
         f = self.lib.immesh_topology_orient_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "topology_orient_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def topology_holes(self, max_edges, max_diagonal=0.0):
+        """immesh_topology_holes on the analysed snapshot: the ordered cycles of the simple boundary loops, and fans over those of at most max_edges
+        edges whose box diagonal is at most max_diagonal (0: any) -> HolesStats; the pass stays on the device for the calls below"""
+        f = self.lib.immesh_topology_holes; f.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.POINTER(HolesStats)]; f.restype = C.c_int
+        st = HolesStats()
+        self._check(f(self.raycaster(), max_edges, max_diagonal, C.byref(st)), "topology_holes")
+        return st
+
+    def topology_holes_loops(self):
+        """the loop tables -> dict: first_vertex, n_edges, status (n_loops,) int32, box (n_loops, 6) float32, cycle_start (n_loops,) int64 (-1: the
+        loop is not simple)"""
+        f = self.lib.immesh_topology_holes_loops; f.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, None, None, 0, C.byref(n)), "topology_holes_loops")
+        out = {"first_vertex": np.empty(n.value, np.int32), "n_edges": np.empty(n.value, np.int32), "status": np.empty(n.value, np.int32),
+               "box": np.empty((n.value, 6), np.float32), "cycle_start": np.empty(n.value, np.int64)}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in ("first_vertex", "n_edges", "status", "box", "cycle_start")], n.value, C.byref(n)),
+                    "topology_holes_loops")
+        return out
+
+    def topology_holes_cycles(self):
+        """the boundary cycles in order: the simple loops' cycles concatenated in loop order -> (n_cycle_vertices,) int32"""
+        f = self.lib.immesh_topology_holes_cycles; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, 0, C.byref(n)), "topology_holes_cycles")
+        out = np.empty(n.value, np.int32)
+        self._check(f(self.raycaster(), _ptr(out), n.value, C.byref(n)), "topology_holes_cycles")
+        return out
+
+    def topology_holes_faces(self):
+        """the fans -> (new_loop (n,) int32, new_faces (n, 3) int32)"""
+        f = self.lib.immesh_topology_holes_faces; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, 0, C.byref(n)), "topology_holes_faces")
+        loop, faces = np.empty(n.value, np.int32), np.empty((n.value, 3), np.int32)
+        self._check(f(self.raycaster(), _ptr(loop), _ptr(faces), n.value, C.byref(n)), "topology_holes_faces")
+        return loop, faces
+
+    def topology_holes_apply(self):
+        """immesh_topology_holes_apply: faces ++ new_faces become the caster's, on the device, and its hierarchy is built again; everything a build
+        discards is discarded"""
+        f = self.lib.immesh_topology_holes_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "topology_holes_apply")
+
+    def topology_holes_timing(self):
+        """device milliseconds of the last (holes pass, apply)"""
+        f = self.lib.immesh_topology_holes_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "topology_holes_last_timing")
         return float(ms[0]), float(ms[1])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------

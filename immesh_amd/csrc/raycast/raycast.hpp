@@ -182,6 +182,26 @@ struct RcOrient {
     }
 };
 
+// the holes of the snapshot's boundary (include/immesh_topology.h, the Holes rule; topology/holes_host.cpp): allocated at the first
+// immesh_topology_holes, never before.  It reads the analysis' sorted half-edges, vparent and loop_cnt in RcTopology.
+struct RcHoles {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // holes, apply: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
+    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+    RcBuf vt, rk_a, rk_b;                                      // per vertex: HV_TABLES int32 arrays, the list ranking's two buffers
+    RcBuf lt, box, cstart;                                     // per loop: HL_TABLES int32 arrays, the box keys, cycle_start as int64
+    RcBuf cycle, cloop, new_faces, new_loop;                   // per boundary edge: the cycles' slots and their loops; the fans' faces and their loops
+    RcBuf merged;                                              // the apply's faces ++ new_faces: it changes places with the caster's face buffer
+    bool have = false;                                         // a holes pass of the current analysis exists
+    int64_t n_loops = 0;                                       // the tables' stride
+    int64_t st[12] = {};                                       // immesh_holes_stats, in its order
+    float ms[2] = {0.0f, 0.0f};
+    ~RcHoles() {
+        rc_destroy_events(ev, 4);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -204,7 +224,10 @@ struct immesh_raycaster {
     RcSample sm;
     RcTopology tp;
     RcOrient ot;
+    RcHoles hl;
 };
+// the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream); it discards what belongs to the snapshot before
+int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces);
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------
 // status[i]: 0 a face, 1 no face within max_dist, 2 the point is not finite.  has_frame == 0: the points are world coordinates.

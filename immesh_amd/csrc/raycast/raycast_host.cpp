@@ -103,6 +103,8 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
     return 0;
 }
 
+}  // namespace
+
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
     r->built = false; r->have_cast = false; r->n_points = 0;
@@ -116,8 +118,6 @@ int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
     r->built = true;
     return 0;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -180,6 +180,7 @@ int immesh_topology_orient_apply(immesh_raycaster* r) {
     r->sm.have = false;
     r->tp.have = false;
     o.have = false;
+    r->hl.have = false;   // the holes pass read the half-edges as they were wound
     return 0;
 }
 

@@ -90,6 +90,53 @@ void ot_launch_decide(hipStream_t s, int64_t n_bound, int32_t mode, int32_t* tab
 void ot_launch_flip(hipStream_t s, const int32_t* faces, int64_t n_faces, const int32_t* patch, const int8_t* base, const int32_t* tab, int64_t n_bound,
                     int8_t* flip, int32_t* faces_out);
 
+// holes (holes_kernels.hip) ---------------------------------------------------------------------------------------------------------------
+// the holes pass' device counters (int64 each; zeroed before every pass)
+enum {
+    HC_N_SIMPLE = 0, HC_N_NONSIMPLE, HC_N_OUTLINE, HC_N_TOO_LONG, HC_N_TOO_WIDE, HC_N_BLOCKED, HC_N_FILLED, HC_N_NEW, HC_N_CLOSED, HC_LARGEST_SIMPLE,
+    HC_N_CYCLE, HC_COUNTERS = 16
+};
+// the per-vertex tables: int32 arrays of n_vtx entries each in one buffer, vt + k * n_vtx.  HV_LAB the loop's label (the root of the analysis'
+// vparent), HV_IN / HV_OUT the boundary half-edges that enter / leave, HV_SUCC / HV_LFACE the head and the face of one that leaves (read where
+// HV_OUT is 1), HV_BAD[label] the loop is not simple, HV_ROOT the vertex is a loop's label, HV_NUM its exclusive prefix sum
+enum { HV_LAB = 0, HV_IN, HV_OUT, HV_SUCC, HV_LFACE, HV_BAD, HV_ROOT, HV_NUM, HV_TABLES };
+// the per-loop tables: int32 arrays of n_loops entries each in one buffer, lt + k * n_loops.  The first three are what immesh_topology_holes_loops
+// returns.  HL_SLEN n_edges of a simple loop, else 0, HL_CSTART its exclusive prefix sum; HL_FILL the new faces of a filled loop, HL_FOFF its sum
+enum { HL_FIRST = 0, HL_NEDGES, HL_STATUS, HL_SLEN, HL_CSTART, HL_BLOCKED, HL_FILL, HL_FOFF, HL_TABLES };
+// one entry of the list ranking: the next vertex on the broken cycle (-1: none) and the distance to it
+struct HlRank { int32_t nxt, d; };
+// HV_LAB by a walk up vparent (the analysis is finished: plain loads), HV_IN = HV_OUT = HV_BAD = 0, HV_SUCC = HV_LFACE = -1
+void hl_launch_init(hipStream_t s, int64_t n_vtx, const int32_t* vparent, int32_t* vt);
+// one lane per sorted half-edge: the head of a run of one, tail t to head h in its face's direction: HV_OUT[t] and HV_IN[h] by integer atomics,
+// HV_SUCC[t] = h and HV_LFACE[t] plain stores
+void hl_launch_degrees(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, int64_t n_vtx, int32_t* vt);
+// HV_BAD[label] = 1 where a boundary vertex is not simple (every writer stores the same value), HV_ROOT
+void hl_launch_flags(hipStream_t s, int64_t n_vtx, int32_t* vt);
+// after the scan of HV_ROOT.  Per vertex of a simple loop: the ranking's start, the cycle broken at its label (the vertex whose successor is the label
+// ends the list).  Per label: HL_FIRST, HL_NEDGES (the analysis' loop_cnt), HL_SLEN, HL_BLOCKED = 0, the box keys preset, and HL_STATUS =
+// NONSIMPLE, OUTLINE (a 3-loop whose three leaving faces are one) or FILLED for now
+void hl_launch_rank_init(hipStream_t s, int64_t n_vtx, const int32_t* vt, const int32_t* loop_cnt, int64_t n_loops, int32_t* lt, uint32_t* box, HlRank* rk);
+// one round of pointer jumping from `in` to `out`: d += d[nxt], nxt = nxt[nxt]; a round reads only what an earlier launch wrote
+void hl_launch_jump(hipStream_t s, int64_t n_vtx, const HlRank* in, HlRank* out);
+// the box keys of the loops from their vertices, folded per wavefront and loop first
+void hl_launch_boxes(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* vt, int64_t n_loops, uint32_t* box);
+// after the scan of HL_SLEN: cycle[HL_CSTART[l] + n_edges - 1 - d] = v and cloop[...] = l for the vertices of the simple loops (n_room entries each)
+void hl_launch_scatter(hipStream_t s, int64_t n_vtx, const int32_t* vt, const HlRank* rk, const int32_t* lt, int64_t n_loops, int32_t* cycle, int32_t* cloop,
+                       int64_t n_room);
+// one lane per loop: TOO_LONG and TOO_WIDE where nothing earlier applies; cstart64[l] (-1: not simple); cnt[HC_N_CYCLE]
+void hl_launch_limits(hipStream_t s, int64_t n_loops, int32_t* lt, const uint32_t* box, int64_t max_edges, double max_diagonal, int64_t* cstart64,
+                      unsigned long long* cnt);
+// one lane per cycle slot (n_room lanes, cnt[HC_N_CYCLE] of them at work): slot k of a loop still FILLED, 2 <= k <= n_edges - 2, looks its chord
+// {v_0, v_k} up in the sorted keys by binary search; found: HL_BLOCKED[l] = 1
+void hl_launch_chords(hipStream_t s, int64_t n_room, const unsigned long long* cnt, const int32_t* cycle, const int32_t* cloop, const unsigned long long* key,
+                      int64_t n_half, int32_t* lt, int64_t n_loops);
+// one lane per loop: the final HL_STATUS, HL_FILL, and the counters of the stats
+void hl_launch_decide(hipStream_t s, int64_t n_loops, int32_t* lt, unsigned long long* cnt);
+// after the scan of HL_FILL, one lane per cycle slot: slot k of a filled loop, 1 <= k <= n_edges - 2, writes new face HL_FOFF[l] + k - 1 =
+// (v_0, v_(k+1), v_k) and its loop (n_room faces of room); cnt[HC_N_NEW]
+void hl_launch_emit(hipStream_t s, int64_t n_room, const int32_t* cycle, const int32_t* cloop, const int32_t* lt, int64_t n_loops, int32_t* new_faces,
+                    int32_t* new_loop, unsigned long long* cnt);
+
 // select ----------------------------------------------------------------------------------------------------------------------------------
 // rank_key[c] = ((2^31 - 1 - nfaces[c]) << 32) | c, iota[c] = c
 void tp_launch_rank_keys(hipStream_t s, const int32_t* nfaces, int64_t n_comp, unsigned long long* rank_key, int32_t* iota);

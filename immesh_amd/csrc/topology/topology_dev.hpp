@@ -1,4 +1,5 @@
-// Device helpers shared by the kernels of the mesh topology: topology_kernels.hip (the analysis) and orient_kernels.hip (the orientation).
+// Device helpers shared by the kernels of the mesh topology: topology_kernels.hip (the analysis), orient_kernels.hip (the orientation) and
+// holes_kernels.hip (the holes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -14,6 +15,13 @@ __device__ __forceinline__ void tp_count(bool pred, unsigned long long* word) {
     const unsigned long long m = __ballot(pred);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(word, (unsigned long long)__popcll(m));
 }
+
+// box keys: order-preserving, as rc_compact_kernel's (topology.hpp has the presets)
+__device__ __forceinline__ uint32_t tp_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float tp_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // ---- union-find ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t tp_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -68,6 +68,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
     int rc;
     q.have = false;
     r->ot.have = false;   // an orientation belongs to the analysis whose half-edges it read
+    r->hl.have = false;   // and so does a holes pass
     if ((rc = tp_events(r))) return rc;
     if ((rc = tp_grow(r, q.cnt, TP_COUNTERS * 8))) return rc;
     if ((rc = tp_grow(r, q.flag, (size_t)nf * 4))) return rc;

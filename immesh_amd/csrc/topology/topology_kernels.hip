@@ -15,15 +15,9 @@
 //   boundary   the boundary heads once more, now that the components are numbered: boundary edges per component, edges per loop
 // All of it integers and min / max: the results do not depend on the order of anything.
 #include "topology.hpp"
-#include "topology_dev.hpp"   // the union-find, the ballot counts and the wavefront folds: the orientation's kernels use them too
+#include "topology_dev.hpp"   // the union-find, the ballot counts, the wavefront folds, the box keys: the orientation's and the holes' kernels use them too
 
 namespace {
-
-__device__ __forceinline__ uint32_t tp_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tp_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // ---- analyse ------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TP_BLOCK) tp_mark_kernel(const int32_t* __restrict__ faces, int64_t n_faces, int64_t n_vtx, int32_t* __restrict__ flag,

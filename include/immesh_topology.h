@@ -1,5 +1,6 @@
 /* immesh_topology.h -- the topology of a built ray caster's snapshot on the device: connected components, open edges, non-manifold and
- * inconsistently wound edges, boundary loops, the Euler characteristic, and a filter that drops small fragments (libimmesh_hip.so).
+ * inconsistently wound edges, boundary loops, the Euler characteristic, a filter that drops small fragments, one winding per manifold patch, and
+ * the boundary cycles in order with a fill of the small holes (libimmesh_hip.so).
  *
  * Reference: none.  The reference writes its mesh to a PLY and leaves "remove isolated pieces" to a desktop tool; nothing pins this module but the
  * contract below and its checker (tests/topology_checker.py: np.unique on the edge keys, a plain union-find loop).
@@ -84,6 +85,48 @@
  * VIEWPOINT a viewpoint of three finite doubles below 2^128 in magnitude; cap >= 0; an orientation of the current analysis before any fetch or apply
  * -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the caster or a new analysis discards the orientation.  Zero faces orient
  * to all zeros; that is not an error.  IMMESH_E_INTERNAL as above; the orientation is void.
+ *
+ * ---- Holes (exact: integers, and min / max of floats for the boxes; as order-free as the above) -------------------------------------------------
+ * immesh_topology_holes gives the ordered cycle of every simple boundary loop of the analysed snapshot and closes the small ones by a fan of new
+ * faces over existing vertices; nothing reaches the caster before _apply.  The rules about counting faces and edges above apply unchanged.
+ *   Boundary half-edge: the one use of an edge with uses == 1, directed as its face traverses it: use k of face (i0, i1, i2) goes from i_k (its
+ *            TAIL) to i_(k+1 mod 3) (its HEAD).
+ *   Loop:    a loop of the analysis: a connected piece of the graph of the boundary edges.  Its LABEL is its smallest vertex index; loops are numbered
+ *            0 .. n_loops - 1 by ascending label, n_loops = the analysis' n_boundary_loops, and n_edges is the loop's number of boundary edges.
+ *   Simple:  a vertex is simple when exactly one boundary half-edge leaves it and exactly one enters it; a loop is simple when all its vertices are,
+ *            and is then one directed cycle.  Its CYCLE is v_0 = the label, v_(j+1) = the head of the half-edge that leaves v_j: n_edges vertices,
+ *            n_edges >= 3.  Two holes that touch in a vertex, neighbours wound against each other and a boundary through a non-manifold vertex are
+ *            not simple: such loops have no cycle and are never filled (orient and apply first: a consistently wound patch has directed borders).
+ *   Box:     lo x y z, hi x y z per loop: per coordinate the smallest and the largest of the FINITE floats among its vertices, +inf / -inf for a
+ *            coordinate without one -- the components' box rule.
+ *   Status:  one per loop, the first that applies:
+ *              IMMESH_HOLE_NONSIMPLE  the loop is not simple;
+ *              IMMESH_HOLE_OUTLINE    its boundary half-edges all belong to one face (a 3-loop: a lone face's own outline, whose fill would be that
+ *                                     face's mirror image);
+ *              IMMESH_HOLE_TOO_LONG   n_edges > max_edges;
+ *              IMMESH_HOLE_TOO_WIDE   max_diagonal > 0 and either the box lacks a finite float in a coordinate or, with
+ *                                     d_k = (double)hi_k - (double)lo_k, (d_x d_x + d_y d_y) + d_z d_z > max_diagonal max_diagonal (IEEE double, in the
+ *                                     order written, no fused multiply-add: Select's arithmetic with the inequality turned round);
+ *              IMMESH_HOLE_BLOCKED    some chord {v_0, v_k}, 2 <= k <= n_edges - 2, is already an edge of the mesh, whatever its uses: the fan would
+ *                                     make it non-manifold;
+ *              IMMESH_HOLE_FILLED     (= 0) otherwise.
+ *   Fill:    a filled loop of n edges gets the n - 2 faces (v_0, v_(k+1), v_k), k = 1 .. n - 2: each traverses its boundary edge against the existing
+ *            use, so the fan is wound like its neighbours.  new_faces lists them loop by loop in loop order, k ascending; new_loop[j] is the loop
+ *            number of new face j.  No vertex is added or moved.
+ *   Invariant: with k filled loops of E boundary edges together, an analysis of faces ++ new_faces has n_boundary - E, n_boundary_loops - k,
+ *            n_edges + E - 3 k, n_counting + E - 2 k, euler + k; n_nonmanifold, n_inconsistent and n_vertices_used unchanged; n_components not
+ *            larger; and a second holes pass with the same limits fills nothing that the first one filled.
+ *   Stats:   n_loops = n_simple + n_nonsimple; the simple ones are n_outline + n_too_long + n_too_wide + n_blocked + n_filled; n_new_faces;
+ *            n_edges_closed (E); largest_simple_loop_edges; n_cycle_vertices = the sum of n_edges over the simple loops.
+ *   Cycles:  cycle_out = the cycles of the simple loops concatenated in loop order; cycle_start[l] = the offset of loop l's cycle in it, -1 for a
+ *            loop that is not simple.
+ *   Apply:   afterwards the caster behaves in every call as one freshly built by immesh_raycast_build_triangles from the same vertices and
+ *            faces ++ new_faces: equal answers bit for bit, and everything a build discards is discarded (the last cast, the samples, the analysis,
+ *            the orientation, the holes).
+ * Validated before any launch: an analysis of the current snapshot; n_vtx <= 2^31 - 1 (the scan over the vertices); max_edges >= 3;
+ * 0 <= max_diagonal finite; cap >= 0; a holes pass of the current analysis before any fetch or apply; for the apply n_faces + n_new <= 2^30 and
+ * 3 (n_faces + n_new) <= 2^31 - 2, so that the result can be analysed -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the
+ * caster, a new analysis or an orient-apply discards the holes pass.  Zero loops give all zeros; that is not an error.
  */
 #ifndef IMMESH_TOPOLOGY_H
 #define IMMESH_TOPOLOGY_H
@@ -164,6 +207,48 @@ int immesh_topology_orient_patches(immesh_raycaster* rc, int32_t* first_face, in
 int immesh_topology_orient_apply(immesh_raycaster* rc);
 /* Device time in milliseconds from HIP events on the caster's stream: [0] the last orient (every launch)  [1] the last apply. */
 int immesh_topology_orient_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] orient  [1] apply */
+
+#define IMMESH_HOLE_FILLED 0
+#define IMMESH_HOLE_NONSIMPLE 1
+#define IMMESH_HOLE_OUTLINE 2
+#define IMMESH_HOLE_TOO_LONG 3
+#define IMMESH_HOLE_TOO_WIDE 4
+#define IMMESH_HOLE_BLOCKED 5
+
+typedef struct immesh_holes_stats {
+    int64_t n_loops;                  /* the analysis' n_boundary_loops */
+    int64_t n_simple;
+    int64_t n_nonsimple;
+    int64_t n_outline;
+    int64_t n_too_long;
+    int64_t n_too_wide;
+    int64_t n_blocked;
+    int64_t n_filled;
+    int64_t n_new_faces;
+    int64_t n_edges_closed;           /* the boundary edges of the filled loops */
+    int64_t largest_simple_loop_edges;
+    int64_t n_cycle_vertices;         /* the sum of n_edges over the simple loops */
+} immesh_holes_stats;
+
+/* The Holes rule on the analysed snapshot; stats may be NULL.  Nothing is allocated or launched for the holes before the first call; the buffers are
+ * grow-only.  The result stays on the device for the calls below until the caster is rebuilt, analysed again, or an apply (this one or the
+ * orientation's) has run.  No read-back lies between its launches. */
+int immesh_topology_holes(immesh_raycaster* rc, int64_t max_edges, double max_diagonal, immesh_holes_stats* stats);
+/* The loop tables, n_loops entries each (box: 6 floats per loop).  Every pointer may be NULL; n_out gets n_loops.  With any array given,
+ * cap < n_loops is IMMESH_E_CAPACITY (n_out is still set). */
+int immesh_topology_holes_loops(immesh_raycaster* rc, int32_t* first_vertex, int32_t* n_edges, int32_t* status, float* box /* 6 per loop */,
+                                int64_t* cycle_start, int64_t cap, int64_t* n_out);
+/* The boundary cycles in order: n_cycle_vertices int32.  cycle_out may be NULL; n_out gets the count.  With it given, cap < the count is
+ * IMMESH_E_CAPACITY. */
+int immesh_topology_holes_cycles(immesh_raycaster* rc, int32_t* cycle_out, int64_t cap, int64_t* n_out);
+/* The new faces: loop_out n_new_faces int32, faces_out 3 per new face; each may be NULL; n_out gets n_new_faces.  With an array given,
+ * cap < n_new_faces is IMMESH_E_CAPACITY. */
+int immesh_topology_holes_faces(immesh_raycaster* rc, int32_t* loop_out, int32_t* faces_out, int64_t cap, int64_t* n_out);
+/* The Apply rule: the faces and the new faces side by side in one device buffer, then the caster's own build; no host round trip of the mesh. */
+int immesh_topology_holes_apply(immesh_raycaster* rc);
+/* Device time in milliseconds from HIP events on the caster's stream: [0] the last holes pass (every launch)  [1] the last apply (the copies and the
+ * build of the hierarchy). */
+int immesh_topology_holes_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] holes  [1] apply */
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,7 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
-Three options look at the mesh itself first (include/immesh_topology.h), all off by default:
+Four options look at the mesh itself first (include/immesh_topology.h), all off by default:
   --min-component-faces N   analyse the mesh, keep the components of at least N faces, rebuild the caster from the kept faces, then evaluate: the floating
                             fragments of noise and moving objects leave the figures
   --topology                the counts of the mesh that is evaluated (components, boundary edges and loops, non-manifold and inconsistent edges,
@@ -15,11 +15,17 @@ Three options look at the mesh itself first (include/immesh_topology.h), all off
                             (immesh_topology_orient), write it over the caster's faces on the device (immesh_topology_orient_apply).  The output gains
                             an `orientation` block with the orientation's counts and a `signed` block from the accuracy query's dist and side: the
                             shares of the ground-truth points in front of, behind and in the plane of their closest face, and the signed mean
+  --fill-holes MAX_EDGES [--fill-max-diagonal D]
+                            after the fragment filter and the orientation, before --topology: analyse the mesh, close every simple boundary loop of at
+                            most MAX_EDGES edges (and, with D > 0, of a box diagonal of at most D) by a fan over its own vertices
+                            (immesh_topology_holes), and give the caster the closed mesh on the device (immesh_topology_holes_apply).  The output gains
+                            a `holes` block with the pass' counts.  Orient first: a border between faces wound against each other is not simple
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
     python tools/mesh_eval.py --cloud gt.npy --ply rec_mesh.ply [--tau 0.05] [--max-dist 1.0] [--density 400] [--seed 0] [--out eval.json]
                               [--min-component-faces N] [--topology] [--orient MODE [--viewpoint X Y Z]]
+                              [--fill-holes MAX_EDGES [--fill-max-diagonal D]]
 """
 import argparse
 import json
@@ -106,6 +112,14 @@ def orient(h, mode, viewpoint=None):
     return out
 
 
+def fill_holes(h, max_edges, max_diagonal=0.0):
+    """h: a HotPath with a built caster -> its small holes closed on the device (analyse, holes, apply); returns (the caster's sizes, the counts)"""
+    h.topology_analyse()
+    st = h.topology_holes(max_edges, max_diagonal)
+    h.topology_holes_apply()
+    return h._raycast_sizes(), {"max_edges": max_edges, "max_diagonal": max_diagonal, **{n: getattr(st, n) for n, _ in capi.HolesStats._fields_}}
+
+
 def topology(h):
     """the counts of the built caster's mesh -> dict"""
     st = h.topology_analyse()
@@ -125,7 +139,11 @@ def main():
     ap.add_argument("--topology", action="store_true", help="add the evaluated mesh's topology counts to the output")
     ap.add_argument("--orient", choices=sorted(ORIENT_MODES), default=None, help="orient every manifold patch consistently before evaluating")
     ap.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --orient viewpoint: the point the faces should face")
+    ap.add_argument("--fill-holes", type=int, default=0, metavar="MAX_EDGES", help="close the simple boundary loops of at most MAX_EDGES edges before evaluating (0: off)")
+    ap.add_argument("--fill-max-diagonal", type=float, default=0.0, metavar="D", help="with --fill-holes: leave the loops whose box diagonal exceeds D (0: any)")
     args = ap.parse_args()
+    if args.fill_max_diagonal and not args.fill_holes:
+        ap.error("--fill-max-diagonal D goes with --fill-holes")
     if (args.orient == "viewpoint") != (args.viewpoint is not None):
         ap.error("--viewpoint X Y Z goes with --orient viewpoint, and only with it")
     cloud = np.load(args.cloud)[:, :3]
@@ -138,6 +156,8 @@ def main():
             sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
         if args.orient:
             extra["orientation"] = orient(h, args.orient, args.viewpoint)
+        if args.fill_holes:
+            sizes, extra["holes"] = fill_holes(h, args.fill_holes, args.fill_max_diagonal)
         if args.topology:
             extra["topology"] = topology(h)
         out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
