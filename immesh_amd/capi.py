@@ -204,6 +204,17 @@ assert C.sizeof(HolesStats) == 96
 HOLE_FILLED, HOLE_NONSIMPLE, HOLE_OUTLINE, HOLE_TOO_LONG, HOLE_TOO_WIDE, HOLE_BLOCKED = 0, 1, 2, 3, 4, 5
 
 
+class SimplifyStats(C.Structure):
+    """immesh_simplify_stats (include/immesh_simplify.h): the counts of the last weld / clustering pass over the caster's snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_vertices_in", "n_vertices_used", "n_alone_not_finite", "n_alone_outside", "n_vertices_out", "largest_cluster",
+                                         "n_faces_in", "n_not_counting", "n_collapsed", "n_duplicate", "n_faces_out")]
+
+
+assert C.sizeof(SimplifyStats) == 88
+SIMPLIFY_FIRST, SIMPLIFY_MEAN = 0, 1
+FACE_KEPT, FACE_NOT_COUNTING, FACE_COLLAPSED, FACE_DUPLICATE = 0, 1, 2, 3
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -1055,6 +1066,56 @@ class HotPath:
         f = self.lib.immesh_topology_holes_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "topology_holes_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    # -- weld and vertex clustering of the caster's snapshot (include/immesh_simplify.h) ---------------------------------------------------------------
+    def simplify(self, cell=0.0, mode=SIMPLIFY_FIRST, merge_duplicates=True):
+        """immesh_simplify on the caster's snapshot: cell == 0 welds the vertices of equal floats, cell > 0 clusters them on a grid (SIMPLIFY_FIRST:
+        the label vertex stays, SIMPLIFY_MEAN: the members' mean); merge_duplicates drops faces over the same three new vertices -> SimplifyStats;
+        the result stays on the device for the calls below"""
+        f = self.lib.immesh_simplify; f.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.POINTER(SimplifyStats)]; f.restype = C.c_int
+        st = SimplifyStats()
+        self._check(f(self.raycaster(), cell, mode, 1 if merge_duplicates else 0, C.byref(st)), "simplify")
+        return st
+
+    def simplify_vertices(self):
+        """the cluster tables -> dict: vtx (n_vertices_out, 3) float32, first_vertex, n_members (n_vertices_out,) int32"""
+        f = self.lib.immesh_simplify_vertices; f.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, 0, C.byref(n)), "simplify_vertices")
+        out = {"vtx": np.empty((n.value, 3), np.float32), "first_vertex": np.empty(n.value, np.int32), "n_members": np.empty(n.value, np.int32)}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in ("vtx", "first_vertex", "n_members")], n.value, C.byref(n)), "simplify_vertices")
+        return out
+
+    def simplify_maps(self):
+        """-> dict: vmap (n_vtx,) int32 (-1: unused), fmap (n_faces,) int32 (-1: not kept), fstatus (n_faces,) int8"""
+        f = self.lib.immesh_simplify_maps; f.argtypes = [C.c_void_p] + [C.c_void_p] * 3; f.restype = C.c_int
+        self._check(f(self.raycaster(), None, None, None), "simplify_maps")
+        nv, nf = self._raycast_sizes()[:2]
+        out = {"vmap": np.empty(nv, np.int32), "fmap": np.empty(nf, np.int32), "fstatus": np.empty(nf, np.int8)}
+        self._check(f(self.raycaster(), _ptr(out["vmap"]), _ptr(out["fmap"]), _ptr(out["fstatus"])), "simplify_maps")
+        return out
+
+    def simplify_faces(self):
+        """the kept faces over the new vertex indices, in face order -> (n_faces_out, 3) int32"""
+        f = self.lib.immesh_simplify_faces; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, 0, C.byref(n)), "simplify_faces")
+        out = np.empty((n.value, 3), np.int32)
+        self._check(f(self.raycaster(), _ptr(out), n.value, C.byref(n)), "simplify_faces")
+        return out
+
+    def simplify_apply(self):
+        """immesh_simplify_apply: vtx_out and faces_out become the caster's, on the device, and its hierarchy is built again; everything a build
+        discards is discarded"""
+        f = self.lib.immesh_simplify_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "simplify_apply")
+
+    def simplify_last_timing(self):
+        """device milliseconds of the last (simplify pass, apply)"""
+        f = self.lib.immesh_simplify_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "simplify_last_timing")
         return float(ms[0]), float(ms[1])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------

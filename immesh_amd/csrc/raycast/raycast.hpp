@@ -202,6 +202,25 @@ struct RcHoles {
     }
 };
 
+// weld and vertex clustering of the snapshot (include/immesh_simplify.h; simplify/simplify_host.cpp): allocated at the first immesh_simplify, never
+// before.  It needs no analysis: it reads the caster's vertex and face buffers.
+struct RcSimplify {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // simplify, apply: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
+    RcBuf cnt;                                                 // 16 int64 (simplify/simplify.hpp names them)
+    RcBuf state, k64, k32, cnum, first, nmem, cstart, vmap;    // per vertex / per cluster (at most one cluster per vertex)
+    RcBuf fk64, fk32, keep, koff, fstatus, fmap;               // per face
+    RcBuf key_a, key_b, k32s, iota, val_a, val_b;              // the sorts' buffers, max(n_vtx, n_faces) entries: the vertices' first, then the faces'
+    RcBuf vtx_out, faces_out;                                  // the result: the apply makes them change places with the caster's buffers
+    bool have = false;                                         // a result of the current snapshot exists
+    int64_t st[11] = {};                                       // immesh_simplify_stats, in its order
+    float ms[2] = {0.0f, 0.0f};
+    ~RcSimplify() {
+        rc_destroy_events(ev, 4);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -225,6 +244,7 @@ struct immesh_raycaster {
     RcTopology tp;
     RcOrient ot;
     RcHoles hl;
+    RcSimplify sp;
 };
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream); it discards what belongs to the snapshot before
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces);

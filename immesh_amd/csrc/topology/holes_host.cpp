@@ -218,6 +218,7 @@ int immesh_topology_holes_apply(immesh_raycaster* r) {
     std::swap(r->faces.bytes, o.merged.bytes);
     o.have = false;
     r->ot.have = false;
+    r->sp.have = false;                                         // (the build discards it too: the faces changed)
     rc = rc_build(r, r->n_vtx, total);                          // discards the last cast, the samples and the analysis; the stream is idle on return
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(o.ev[3], s));

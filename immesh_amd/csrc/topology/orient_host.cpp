@@ -181,6 +181,7 @@ int immesh_topology_orient_apply(immesh_raycaster* r) {
     r->tp.have = false;
     o.have = false;
     r->hl.have = false;   // the holes pass read the half-edges as they were wound
+    r->sp.have = false;   // a simplification mapped the faces as they were
     return 0;
 }
 

@@ -5,7 +5,12 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
-Four options look at the mesh itself first (include/immesh_topology.h), all off by default:
+Five options look at the mesh itself first (include/immesh_simplify.h, include/immesh_topology.h), all off by default:
+  --weld | --simplify CELL [--simplify-mode first|mean] [--keep-duplicate-faces]
+                            first of all, before the fragment filter: weld the vertices of equal coordinates (--weld: a soup that repeats its vertices
+                            becomes a mesh whose faces share indices) or cluster them on a grid of CELL (--simplify: the decimation), drop the faces
+                            that collapse and, unless --keep-duplicate-faces, the faces given twice (immesh_simplify), and give the caster the result
+                            on the device (immesh_simplify_apply).  The output gains a `simplify` block: the arguments and the pass' counts
   --min-component-faces N   analyse the mesh, keep the components of at least N faces, rebuild the caster from the kept faces, then evaluate: the floating
                             fragments of noise and moving objects leave the figures
   --topology                the counts of the mesh that is evaluated (components, boundary edges and loops, non-manifold and inconsistent edges,
@@ -26,6 +31,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
     python tools/mesh_eval.py --cloud gt.npy --ply rec_mesh.ply [--tau 0.05] [--max-dist 1.0] [--density 400] [--seed 0] [--out eval.json]
                               [--min-component-faces N] [--topology] [--orient MODE [--viewpoint X Y Z]]
                               [--fill-holes MAX_EDGES [--fill-max-diagonal D]]
+                              [--weld | --simplify CELL [--simplify-mode first|mean]] [--keep-duplicate-faces]
 """
 import argparse
 import json
@@ -120,6 +126,19 @@ def fill_holes(h, max_edges, max_diagonal=0.0):
     return h._raycast_sizes(), {"max_edges": max_edges, "max_diagonal": max_diagonal, **{n: getattr(st, n) for n, _ in capi.HolesStats._fields_}}
 
 
+SIMPLIFY_MODES = {"first": capi.SIMPLIFY_FIRST, "mean": capi.SIMPLIFY_MEAN}
+
+
+def simplify(h, cell, mode="first", merge_duplicates=True):
+    """h: a HotPath with a built caster -> its snapshot welded (cell == 0) or clustered on a grid of `cell` on the device (simplify, apply); returns
+    (the caster's sizes, the new vertices and faces as the later steps need them on the host, the arguments and the counts)"""
+    st = h.simplify(cell, SIMPLIFY_MODES[mode], merge_duplicates)
+    vtx, faces = h.simplify_vertices()["vtx"], h.simplify_faces()
+    h.simplify_apply()
+    return h._raycast_sizes(), vtx, faces, {"cell": cell, "mode": mode, "merge_duplicates": bool(merge_duplicates),
+                                            **{n: getattr(st, n) for n, _ in capi.SimplifyStats._fields_}}
+
+
 def topology(h):
     """the counts of the built caster's mesh -> dict"""
     st = h.topology_analyse()
@@ -141,7 +160,15 @@ def main():
     ap.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --orient viewpoint: the point the faces should face")
     ap.add_argument("--fill-holes", type=int, default=0, metavar="MAX_EDGES", help="close the simple boundary loops of at most MAX_EDGES edges before evaluating (0: off)")
     ap.add_argument("--fill-max-diagonal", type=float, default=0.0, metavar="D", help="with --fill-holes: leave the loops whose box diagonal exceeds D (0: any)")
+    ap.add_argument("--weld", action="store_true", help="weld the vertices of equal coordinates first of all (--simplify 0)")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a grid of CELL first of all (0: the weld)")
+    ap.add_argument("--simplify-mode", choices=sorted(SIMPLIFY_MODES), default="first", help="with --simplify: a cluster's position, its first vertex or the mean")
+    ap.add_argument("--keep-duplicate-faces", action="store_true", help="with --weld / --simplify: keep the faces given twice")
     args = ap.parse_args()
+    if args.weld and args.simplify is not None:
+        ap.error("--weld is --simplify 0: give one of them")
+    if (args.keep_duplicate_faces or args.simplify_mode != "first") and not args.weld and args.simplify is None:
+        ap.error("--simplify-mode and --keep-duplicate-faces go with --weld or --simplify CELL")
     if args.fill_max_diagonal and not args.fill_holes:
         ap.error("--fill-max-diagonal D goes with --fill-holes")
     if (args.orient == "viewpoint") != (args.viewpoint is not None):
@@ -152,6 +179,8 @@ def main():
     try:
         sizes = h.raycast_build_triangles(vtx, faces)
         extra = {}
+        if args.weld or args.simplify is not None:
+            sizes, vtx, faces, extra["simplify"] = simplify(h, 0.0 if args.weld else args.simplify, args.simplify_mode, not args.keep_duplicate_faces)
         if args.min_component_faces > 0:
             sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
         if args.orient:
