@@ -215,6 +215,17 @@ SIMPLIFY_FIRST, SIMPLIFY_MEAN = 0, 1
 FACE_KEPT, FACE_NOT_COUNTING, FACE_COLLAPSED, FACE_DUPLICATE = 0, 1, 2, 3
 
 
+class SmoothStats(C.Structure):
+    """immesh_smooth_stats (include/immesh_smooth.h): the counts of the last smoothing pass over the caster's snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_vertices", "n_used", "n_not_finite", "n_border", "n_interior", "n_moving", "n_pairs", "max_valence", "n_steps",
+                                         "n_held", "n_moved")] + [("max_disp2", C.c_double)]
+
+
+assert C.sizeof(SmoothStats) == 96
+VERTEX_UNUSED, VERTEX_NOT_FINITE, VERTEX_BORDER, VERTEX_INTERIOR = 0, 1, 2, 3
+SMOOTH_BORDER_FIXED, SMOOTH_BORDER_ALONG, SMOOTH_BORDER_FREE = 0, 1, 2
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -1117,6 +1128,56 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "simplify_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- the one-ring table, Taubin smoothing and vertex normals of the caster's snapshot (include/immesh_smooth.h) -----------------------------------
+    def smooth(self, n_steps=10, lam=0.5, mu=-0.53, border=SMOOTH_BORDER_FIXED):
+        """immesh_smooth on the caster's snapshot: the one-ring table, the vertex classes and n_steps Jacobi steps with the factor lam on even and mu
+        on odd steps (Taubin: mu < -lam < 0; Laplace: mu == lam); border says what a BORDER vertex averages over -> SmoothStats; the result stays on
+        the device for the calls below"""
+        f = self.lib.immesh_smooth; f.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(SmoothStats)]; f.restype = C.c_int
+        st = SmoothStats()
+        self._check(f(self.raycaster(), n_steps, lam, mu, border, C.byref(st)), "smooth")
+        return st
+
+    def smooth_vertices(self):
+        """-> dict: vtx (n_vtx, 3) float32 (the positions after the last step), vclass (n_vtx,) int8"""
+        f = self.lib.immesh_smooth_vertices; f.argtypes = [C.c_void_p] + [C.c_void_p] * 2; f.restype = C.c_int
+        self._check(f(self.raycaster(), None, None), "smooth_vertices")
+        nv = self._raycast_sizes()[0]
+        out = {"vtx": np.empty((nv, 3), np.float32), "vclass": np.empty(nv, np.int8)}
+        self._check(f(self.raycaster(), _ptr(out["vtx"]), _ptr(out["vclass"])), "smooth_vertices")
+        return out
+
+    def smooth_adjacency(self):
+        """the one-ring table -> dict: row_start (n_vtx + 1,) int64, neighbours, uses (n_pairs,) int32"""
+        f = self.lib.immesh_smooth_adjacency; f.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, 0, C.byref(n)), "smooth_adjacency")
+        nv = self._raycast_sizes()[0]
+        out = {"row_start": np.empty(nv + 1, np.int64), "neighbours": np.empty(n.value, np.int32), "uses": np.empty(n.value, np.int32)}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in ("row_start", "neighbours", "uses")], n.value, C.byref(n)), "smooth_adjacency")
+        return out
+
+    def smooth_apply(self):
+        """immesh_smooth_apply: the smoothed positions become the caster's, on the device, and its hierarchy is built again; everything a build
+        discards is discarded"""
+        f = self.lib.immesh_smooth_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "smooth_apply")
+
+    def smooth_last_timing(self):
+        """device milliseconds of the last (one-ring and classes, steps, apply)"""
+        f = self.lib.immesh_smooth_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.raycaster(), ms), "smooth_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def vertex_normals(self, fetch=True):
+        """immesh_vertex_normals of the caster's current snapshot -> (normals (n_vtx, 3) float32, or None without fetch; n_zero)"""
+        f = self.lib.immesh_vertex_normals; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        out = np.empty((self._raycast_sizes()[0], 3), np.float32) if fetch else None
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), _ptr(out) if fetch else None, C.byref(n)), "vertex_normals")
+        return out, n.value
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

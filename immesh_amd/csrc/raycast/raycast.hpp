@@ -221,6 +221,30 @@ struct RcSimplify {
     }
 };
 
+// the one-ring table, Taubin smoothing and vertex normals of the snapshot (include/immesh_smooth.h; smooth/smooth_host.cpp): allocated at the first
+// immesh_smooth (the normals' incidence table at the first immesh_vertex_normals), never before.  It needs no analysis: it reads the caster's vertex
+// and face buffers.
+struct RcSmooth {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // one-ring, steps, apply: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
+    RcBuf cnt;                                                 // 16 int64 (smooth/smooth.hpp names them)
+    RcBuf key_a, key_b, val_a, val_b;                          // the directed pairs, 6 n_faces: _b sorted; _a holds the heads and their scan afterwards
+    RcBuf rstart;                                              // per run of equal keys, and one more
+    RcBuf neighbours, uses, sn;                                // per entry of the one-ring (at most 6 n_faces); sn: the neighbour, or -1 outside S(v)
+    RcBuf row_start, vclass, flag;                             // per vertex: int64 (and one more), int8, SM_FLAGS int8 arrays
+    RcBuf pos[2];                                              // the steps' two position buffers; pos[cur] is vtx_out
+    RcBuf nkey_a, nkey_b, nval_a, nval_b, normals;             // the normals: (vertex, face) pairs, 3 n_faces; 3 floats per vertex
+    int cur = 0;
+    bool have = false;                                         // a result of the current snapshot exists
+    int64_t st[11] = {};                                       // immesh_smooth_stats' integers, in its order
+    double max_disp2 = 0.0;
+    float ms[3] = {0.0f, 0.0f, 0.0f};                          // one-ring and classes, steps, apply
+    ~RcSmooth() {
+        rc_destroy_events(ev, 6);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -245,6 +269,7 @@ struct immesh_raycaster {
     RcOrient ot;
     RcHoles hl;
     RcSimplify sp;
+    RcSmooth so;
 };
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream); it discards what belongs to the snapshot before
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces);

@@ -111,6 +111,7 @@ int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
     r->sm.have = false;   // samples belong to the snapshot they were drawn from
     r->tp.have = false;   // and so does the topology's analysis
     r->sp.have = false;   // and a simplification's result
+    r->so.have = false;   // and a smoothing pass'
     const RcLeaves src = {(const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p};
     const int rc = rc_tree_build(r->ctx, "raycast", r->s, r->ev[0], r->ev[1], r->h_small, r->tree, n_faces, src);
     if (rc) return rc;

@@ -236,6 +236,7 @@ int immesh_simplify_apply(immesh_raycaster* r) {
     o.have = false;
     r->ot.have = false;
     r->hl.have = false;
+    r->so.have = false;                                         // (the build discards a smoothing pass too)
     rc = rc_build(r, nv, nf);                                   // discards the last cast, the samples and the analysis; the stream is idle on return
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(o.ev[3], s));

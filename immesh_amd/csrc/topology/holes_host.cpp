@@ -219,6 +219,7 @@ int immesh_topology_holes_apply(immesh_raycaster* r) {
     o.have = false;
     r->ot.have = false;
     r->sp.have = false;                                         // (the build discards it too: the faces changed)
+    r->so.have = false;                                         // (and a smoothing pass)
     rc = rc_build(r, r->n_vtx, total);                          // discards the last cast, the samples and the analysis; the stream is idle on return
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(o.ev[3], s));

@@ -182,6 +182,7 @@ int immesh_topology_orient_apply(immesh_raycaster* r) {
     o.have = false;
     r->hl.have = false;   // the holes pass read the half-edges as they were wound
     r->sp.have = false;   // a simplification mapped the faces as they were
+    r->so.have = false;   // a smoothing pass belongs to the snapshot as it was
     return 0;
 }
 

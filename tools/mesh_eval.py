@@ -5,7 +5,7 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
-Five options look at the mesh itself first (include/immesh_simplify.h, include/immesh_topology.h), all off by default:
+Six options look at the mesh itself first (include/immesh_simplify.h, include/immesh_topology.h, include/immesh_smooth.h), all off by default:
   --weld | --simplify CELL [--simplify-mode first|mean] [--keep-duplicate-faces]
                             first of all, before the fragment filter: weld the vertices of equal coordinates (--weld: a soup that repeats its vertices
                             becomes a mesh whose faces share indices) or cluster them on a grid of CELL (--simplify: the decimation), drop the faces
@@ -25,6 +25,11 @@ Five options look at the mesh itself first (include/immesh_simplify.h, include/i
                             most MAX_EDGES edges (and, with D > 0, of a box diagonal of at most D) by a fan over its own vertices
                             (immesh_topology_holes), and give the caster the closed mesh on the device (immesh_topology_holes_apply).  The output gains
                             a `holes` block with the pass' counts.  Orient first: a border between faces wound against each other is not simple
+  --smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]
+                            after the weld, the fragment filter, the orientation and the fill, before --topology and the sampling: N_STEPS steps of
+                            Taubin smoothing over the one-ring (immesh_smooth; L = 0.5 and M = -0.53 by default, M = L is plain Laplacian smoothing;
+                            the border vertices stay, slide along the border or move freely), and the caster gets the moved vertices on the device
+                            (immesh_smooth_apply).  The output gains a `smooth` block: the arguments and the pass' counts
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
@@ -32,6 +37,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--min-component-faces N] [--topology] [--orient MODE [--viewpoint X Y Z]]
                               [--fill-holes MAX_EDGES [--fill-max-diagonal D]]
                               [--weld | --simplify CELL [--simplify-mode first|mean]] [--keep-duplicate-faces]
+                              [--smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]]
 """
 import argparse
 import json
@@ -139,6 +145,16 @@ def simplify(h, cell, mode="first", merge_duplicates=True):
                                             **{n: getattr(st, n) for n, _ in capi.SimplifyStats._fields_}}
 
 
+SMOOTH_BORDERS = {"fixed": capi.SMOOTH_BORDER_FIXED, "along": capi.SMOOTH_BORDER_ALONG, "free": capi.SMOOTH_BORDER_FREE}
+
+
+def smooth(h, n_steps, lam=0.5, mu=-0.53, border="fixed"):
+    """h: a HotPath with a built caster -> its vertices smoothed on the device (smooth, apply); returns the arguments and the counts"""
+    st = h.smooth(n_steps, lam, mu, SMOOTH_BORDERS[border])
+    h.smooth_apply()
+    return {"lambda": lam, "mu": mu, "border": border, **{n: getattr(st, n) for n, _ in capi.SmoothStats._fields_}}
+
+
 def topology(h):
     """the counts of the built caster's mesh -> dict"""
     st = h.topology_analyse()
@@ -164,7 +180,15 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="cluster the vertices on a grid of CELL first of all (0: the weld)")
     ap.add_argument("--simplify-mode", choices=sorted(SIMPLIFY_MODES), default="first", help="with --simplify: a cluster's position, its first vertex or the mean")
     ap.add_argument("--keep-duplicate-faces", action="store_true", help="with --weld / --simplify: keep the faces given twice")
+    ap.add_argument("--smooth", type=int, default=None, metavar="N_STEPS", help="smooth the vertices over their one-rings before sampling")
+    ap.add_argument("--smooth-lambda", type=float, default=None, metavar="L", help="with --smooth: the factor of the even steps (0.5)")
+    ap.add_argument("--smooth-mu", type=float, default=None, metavar="M", help="with --smooth: the factor of the odd steps (-0.53; M = L: Laplacian smoothing)")
+    ap.add_argument("--smooth-border", choices=sorted(SMOOTH_BORDERS), default=None, help="with --smooth: what a border vertex does (fixed)")
     args = ap.parse_args()
+    if args.smooth is None and (args.smooth_lambda is not None or args.smooth_mu is not None or args.smooth_border is not None):
+        ap.error("--smooth-lambda, --smooth-mu and --smooth-border go with --smooth N_STEPS")
+    if args.smooth is not None and args.smooth < 0:
+        ap.error("--smooth N_STEPS: not negative")
     if args.weld and args.simplify is not None:
         ap.error("--weld is --simplify 0: give one of them")
     if (args.keep_duplicate_faces or args.simplify_mode != "first") and not args.weld and args.simplify is None:
@@ -187,6 +211,9 @@ def main():
             extra["orientation"] = orient(h, args.orient, args.viewpoint)
         if args.fill_holes:
             sizes, extra["holes"] = fill_holes(h, args.fill_holes, args.fill_max_diagonal)
+        if args.smooth is not None:
+            extra["smooth"] = smooth(h, args.smooth, 0.5 if args.smooth_lambda is None else args.smooth_lambda, -0.53 if args.smooth_mu is None else args.smooth_mu,
+                                     args.smooth_border or "fixed")
         if args.topology:
             extra["topology"] = topology(h)
         out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
