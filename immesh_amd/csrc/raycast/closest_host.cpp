@@ -80,11 +80,11 @@ int immesh_closest_points(immesh_raycaster* r, const immesh_ray_frame* frame, co
     immesh_ctx* c = r->ctx;
     RcClosest& cl = r->cl;
     RcDist& q = cl.q;
-    if (!r->built) { c->err = "closest_points: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    int rc;
+    if ((rc = rc_built(r, "closest_points"))) return rc;
     if (n_pts < 0 || n_pts > (int64_t)0x7FFFFFFE || (n_pts > 0 && !pts)) { c->err = "closest_points: bad point array"; return IMMESH_E_INVAL; }
     if (!(max_dist > 0.0) || !std::isfinite(max_dist)) { c->err = "closest_points: need 0 < max_dist, finite"; return IMMESH_E_INVAL; }
     RcFrame fr = {};
-    int rc;
     if (frame && (rc = rc_frame(c, "closest_points", frame, &fr))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;

@@ -177,11 +177,11 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     RcSample& q = r->sm;
-    if (!r->built) { c->err = "mesh_sample: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    int rc;
+    if ((rc = rc_built(r, "mesh_sample"))) return rc;
     if (!(density > 0.0) || !std::isfinite(density)) { c->err = "mesh_sample: need 0 < density, finite"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
-    int rc;
     q.have = false; q.n = 0;
     if ((rc = ms_events(r))) return rc;
     const int64_t nf = r->n_faces;

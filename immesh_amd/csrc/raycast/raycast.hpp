@@ -2,6 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <utility>
+#include "../../../include/immesh_closest.h"     // (and immesh_raycast.h): the frame and the distance statistics
+#include "../../../include/immesh_topology.h"    // the stats the passes' records hold
+#include "../../../include/immesh_simplify.h"
+#include "../../../include/immesh_smooth.h"
 
 constexpr int RC_BLOCK = 256;
 // The sort key of a face is (Morton code of its box centre, position among the faces that enter the tree): RC_CODE_BITS + RC_INDEX_BITS bits, all
@@ -70,9 +75,6 @@ void rc_launch_points(hipStream_t s, const RcFrame& fr, const float* dirs, const
                       float* cells, int32_t* keep);
 
 // ---- the host records: each releases what it holds when it is destroyed, so a buffer is freed by being a member --------------------------------------
-struct immesh_ctx;
-struct immesh_ray_frame;
-struct immesh_closest_stats;
 struct RcBuf {   // grow-only device buffer
     void* p = nullptr;
     size_t bytes = 0;
@@ -81,14 +83,29 @@ struct RcBuf {   // grow-only device buffer
     RcBuf& operator=(const RcBuf&) = delete;
     ~RcBuf() { if (p) (void)hipFree(p); }
 };
+inline void rc_swap(RcBuf& a, RcBuf& b) {   // two buffers change places (an apply: a result becomes the snapshot)
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+}
 inline void rc_destroy_events(hipEvent_t* e, int n) {
     for (int i = 0; i < n; i++)
         if (e[i]) (void)hipEventDestroy(e[i]);
+}
+inline int rc_index_bits(int64_t n) {   // the bits the values 0 .. n - 1 need: the significant bits of a sort over them
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
+    return bits;
 }
 // grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with "<who>: hipMalloc(... B) failed" in the context
 int rc_grow(immesh_ctx* c, const char* who, RcBuf& b, size_t bytes);
 // checks a frame (twelve finite values; "<who>: frame rotation / position is not finite") and copies it
 int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr);
+// dst = `bytes` of device memory, unless dst is NULL or nothing is asked for
+int rc_fetch(immesh_ctx* c, void* dst, const void* src, size_t bytes);
+// the room of a fetch.  rc_cap_negative: "<who>: cap is negative".  rc_cap: that check, then *n_out = n (when given) and, when an output is wanted,
+// "<who>: cap <cap> < <n> <noun>" (IMMESH_E_CAPACITY)
+int rc_cap_negative(immesh_ctx* c, const char* who, int64_t cap);
+int rc_cap(immesh_ctx* c, const char* who, int64_t cap, int64_t n, int64_t* n_out, bool wanted, const char* noun);
 
 // a hierarchy and the scratch of its build: the caster's over faces, the cloud index's over points
 struct RcTree {
@@ -142,92 +159,70 @@ struct RcSample {
     }
 };
 
+// What the five passes over the snapshot share (analysis, orientation, holes, simplification, smoothing): the events of their spans, the device
+// counters and their pinned copy, all created by rc_pass_ready at the pass' first call and never before; `have`: a result of the current snapshot (of
+// the current analysis, for the orientation and the holes) exists.  rc_snapshot_changed / rc_analysis_changed below clear it.
+struct RcPass {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of up to three spans
+    unsigned long long* h_cnt = nullptr;                       // pinned: the counters, and what the pass asks for behind them
+    RcBuf cnt;                                                 // n_cnt int64 (the pass' header names them)
+    const char* who = "";                                      // the prefix of the pass' rc_grow messages
+    int n_cnt = 0;
+    bool have = false;
+    float ms[3] = {0.0f, 0.0f, 0.0f};                          // the spans' device time
+    ~RcPass() {
+        rc_destroy_events(ev, 6);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the topology of the snapshot (include/immesh_topology.h; topology/topology_host.cpp): allocated at the first immesh_topology_analyse, never before
-struct RcTopology {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // analyse, select: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the counters, and [16] / [17] the two words of n_counting
-    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+struct RcTopology : RcPass {                                   // spans: analyse, select; pinned [16] / [17]: the two words of n_counting
     RcBuf flag, off, used, parent, vparent, loop_cnt;          // per face / per vertex
     RcBuf key_a, key_b, val_a, val_b;                          // the half-edges; _b sorted (kept for the edge lists)
     RcBuf label, root, num, comp;                              // per face
     RcBuf first, nfaces, nbound, box;                          // per component (sized by the counting faces)
     RcBuf head, eid, start, pick, poff, uv, uses;              // edge lists
     RcBuf rank_a, rank_b, iota_a, iota_b, keepc, keep32, keep8, koff, out;   // select
-    bool have = false;                                         // an analysis of the current snapshot exists
     int64_t n_counting = 0, n_half = 0;
-    int64_t st[14] = {};                                       // immesh_topology_stats, in its order
-    float ms[2] = {0.0f, 0.0f};
-    ~RcTopology() {
-        rc_destroy_events(ev, 4);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
+    immesh_topology_stats st = {};
 };
 
 // the orientation of the snapshot's manifold patches (include/immesh_topology.h; topology/orient_host.cpp): allocated at the first
 // immesh_topology_orient, never before.  It reads the analysis' flag and sorted half-edges in RcTopology.
-struct RcOrient {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // orient, apply: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
-    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+struct RcOrient : RcPass {                                     // spans: orient, apply
     RcBuf cover;                                               // the double cover's parents: node 2 f + s is face f with flip s
     RcBuf label, base, root, num, patch, flip, out;            // per face (base, flip: int8; out: the oriented faces)
     RcBuf tab;                                                 // per patch, OT_TABLES int32 arrays of n_counting entries each
-    bool have = false;                                         // an orientation of the current analysis exists
     int64_t n_bound = 0;                                       // the tables' stride: the analysis' counting faces
-    int64_t st[9] = {};                                        // immesh_orient_stats, in its order
-    float ms[2] = {0.0f, 0.0f};
-    ~RcOrient() {
-        rc_destroy_events(ev, 4);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
+    immesh_orient_stats st = {};
 };
 
 // the holes of the snapshot's boundary (include/immesh_topology.h, the Holes rule; topology/holes_host.cpp): allocated at the first
 // immesh_topology_holes, never before.  It reads the analysis' sorted half-edges, vparent and loop_cnt in RcTopology.
-struct RcHoles {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // holes, apply: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
-    RcBuf cnt;                                                 // 16 int64 (topology/topology.hpp names them)
+struct RcHoles : RcPass {                                      // spans: holes, apply
     RcBuf vt, rk_a, rk_b;                                      // per vertex: HV_TABLES int32 arrays, the list ranking's two buffers
     RcBuf lt, box, cstart;                                     // per loop: HL_TABLES int32 arrays, the box keys, cycle_start as int64
     RcBuf cycle, cloop, new_faces, new_loop;                   // per boundary edge: the cycles' slots and their loops; the fans' faces and their loops
     RcBuf merged;                                              // the apply's faces ++ new_faces: it changes places with the caster's face buffer
-    bool have = false;                                         // a holes pass of the current analysis exists
     int64_t n_loops = 0;                                       // the tables' stride
-    int64_t st[12] = {};                                       // immesh_holes_stats, in its order
-    float ms[2] = {0.0f, 0.0f};
-    ~RcHoles() {
-        rc_destroy_events(ev, 4);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
+    immesh_holes_stats st = {};
 };
 
 // weld and vertex clustering of the snapshot (include/immesh_simplify.h; simplify/simplify_host.cpp): allocated at the first immesh_simplify, never
 // before.  It needs no analysis: it reads the caster's vertex and face buffers.
-struct RcSimplify {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // simplify, apply: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
-    RcBuf cnt;                                                 // 16 int64 (simplify/simplify.hpp names them)
+struct RcSimplify : RcPass {                                   // spans: simplify, apply
     RcBuf state, k64, k32, cnum, first, nmem, cstart, vmap;    // per vertex / per cluster (at most one cluster per vertex)
     RcBuf fk64, fk32, keep, koff, fstatus, fmap;               // per face
     RcBuf key_a, key_b, k32s, iota, val_a, val_b;              // the sorts' buffers, max(n_vtx, n_faces) entries: the vertices' first, then the faces'
     RcBuf vtx_out, faces_out;                                  // the result: the apply makes them change places with the caster's buffers
-    bool have = false;                                         // a result of the current snapshot exists
-    int64_t st[11] = {};                                       // immesh_simplify_stats, in its order
-    float ms[2] = {0.0f, 0.0f};
-    ~RcSimplify() {
-        rc_destroy_events(ev, 4);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
+    immesh_simplify_stats st = {};
 };
 
 // the one-ring table, Taubin smoothing and vertex normals of the snapshot (include/immesh_smooth.h; smooth/smooth_host.cpp): allocated at the first
 // immesh_smooth (the normals' incidence table at the first immesh_vertex_normals), never before.  It needs no analysis: it reads the caster's vertex
 // and face buffers.
-struct RcSmooth {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // one-ring, steps, apply: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the counters
-    RcBuf cnt;                                                 // 16 int64 (smooth/smooth.hpp names them)
+struct RcSmooth : RcPass {                                     // spans: one-ring and classes, steps, apply
     RcBuf key_a, key_b, val_a, val_b;                          // the directed pairs, 6 n_faces: _b sorted; _a holds the heads and their scan afterwards
     RcBuf rstart;                                              // per run of equal keys, and one more
     RcBuf neighbours, uses, sn;                                // per entry of the one-ring (at most 6 n_faces); sn: the neighbour, or -1 outside S(v)
@@ -235,14 +230,7 @@ struct RcSmooth {
     RcBuf pos[2];                                              // the steps' two position buffers; pos[cur] is vtx_out
     RcBuf nkey_a, nkey_b, nval_a, nval_b, normals;             // the normals: (vertex, face) pairs, 3 n_faces; 3 floats per vertex
     int cur = 0;
-    bool have = false;                                         // a result of the current snapshot exists
-    int64_t st[11] = {};                                       // immesh_smooth_stats' integers, in its order
-    double max_disp2 = 0.0;
-    float ms[3] = {0.0f, 0.0f, 0.0f};                          // one-ring and classes, steps, apply
-    ~RcSmooth() {
-        rc_destroy_events(ev, 6);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
+    immesh_smooth_stats st = {};
 };
 
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
@@ -273,6 +261,22 @@ struct immesh_raycaster {
 };
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream); it discards what belongs to the snapshot before
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces);
+// the discard rule (its table stands above them in raycast_host.cpp): what read the snapshot, and what read the analysis
+void rc_snapshot_changed(immesh_raycaster* r);
+void rc_analysis_changed(immesh_raycaster* r);
+// the state an entry point needs, each refusal with the caller's name in front: a hierarchy has been built; that, and an analysis of the snapshot
+// exists; p holds a result ("<who>: <none>" otherwise)
+int rc_built(immesh_raycaster* r, const char* who);
+int rc_analysed(immesh_raycaster* r, const char* who);
+int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none);
+// A pass on the caster's stream.  ready: the events and n_pinned pinned words if absent, the n_cnt device counters; `who` prefixes the messages of
+// this and every later rc_pass_grow.  begin: ev[e0] recorded, the counters zeroed.  end: ev[e1] recorded, the counters [first, first + n) copied to
+// h_cnt, the launches' error checked, the stream idle, ms[span] = e0 .. e1.  span: an end without counters (an apply).
+int rc_pass_ready(immesh_raycaster* r, const char* who, RcPass& p, int n_cnt, int n_pinned);
+int rc_pass_grow(immesh_raycaster* r, const RcPass& p, RcBuf& b, size_t bytes);
+int rc_pass_begin(immesh_raycaster* r, RcPass& p, int e0);
+int rc_pass_end(immesh_raycaster* r, RcPass& p, int e0, int e1, int span, int first, int n);
+int rc_pass_span(immesh_raycaster* r, RcPass& p, int e0, int e1, int span);
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------
 // status[i]: 0 a face, 1 no face within max_dist, 2 the point is not finite.  has_frame == 0: the points are world coordinates.

@@ -33,6 +33,78 @@ int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFr
     return 0;
 }
 
+int rc_fetch(immesh_ctx* c, void* dst, const void* src, size_t bytes) {
+    if (dst && bytes > 0) HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rc_cap_negative(immesh_ctx* c, const char* who, int64_t cap) {
+    if (cap < 0) { c->err = std::string(who) + ": cap is negative"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_cap(immesh_ctx* c, const char* who, int64_t cap, int64_t n, int64_t* n_out, bool wanted, const char* noun) {
+    const int rc = rc_cap_negative(c, who, cap);
+    if (rc) return rc;
+    if (n_out) *n_out = n;
+    if (wanted && cap < n) {
+        c->err = std::string(who) + ": cap " + std::to_string(cap) + " < " + std::to_string(n) + " " + noun;
+        return IMMESH_E_CAPACITY;
+    }
+    return 0;
+}
+
+int rc_built(immesh_raycaster* r, const char* who) {
+    if (!r->built) { r->ctx->err = std::string(who) + ": no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_analysed(immesh_raycaster* r, const char* who) {
+    const int rc = rc_built(r, who);
+    if (rc) return rc;
+    if (!r->tp.have) { r->ctx->err = std::string(who) + ": no analysis since the caster's last build (immesh_topology_analyse)"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none) {
+    if (!p.have) { r->ctx->err = std::string(who) + ": " + none; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_pass_ready(immesh_raycaster* r, const char* who, RcPass& p, int n_cnt, int n_pinned) {
+    immesh_ctx* c = r->ctx;
+    for (hipEvent_t& e : p.ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (!p.h_cnt) HIPCHK(c, hipHostMalloc((void**)&p.h_cnt, (size_t)n_pinned * 8));
+    p.who = who; p.n_cnt = n_cnt;
+    return rc_pass_grow(r, p, p.cnt, (size_t)n_cnt * 8);
+}
+
+int rc_pass_grow(immesh_raycaster* r, const RcPass& p, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, p.who, b, bytes); }
+
+int rc_pass_begin(immesh_raycaster* r, RcPass& p, int e0) {
+    HIPCHK(r->ctx, hipEventRecord(p.ev[e0], r->s));
+    HIPCHK(r->ctx, hipMemsetAsync(p.cnt.p, 0, (size_t)p.n_cnt * 8, r->s));
+    return 0;
+}
+
+int rc_pass_end(immesh_raycaster* r, RcPass& p, int e0, int e1, int span, int first, int n) {
+    immesh_ctx* c = r->ctx;
+    HIPCHK(c, hipEventRecord(p.ev[e1], r->s));
+    HIPCHK(c, hipMemcpyAsync(p.h_cnt + first, (const unsigned long long*)p.cnt.p + first, (size_t)n * 8, hipMemcpyDeviceToHost, r->s));   // the read-back
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(r->s));
+    (void)hipEventElapsedTime(&p.ms[span], p.ev[e0], p.ev[e1]);
+    return 0;
+}
+
+int rc_pass_span(immesh_raycaster* r, RcPass& p, int e0, int e1, int span) {
+    HIPCHK(r->ctx, hipEventRecord(p.ev[e1], r->s));
+    HIPCHK(r->ctx, hipStreamSynchronize(r->s));
+    (void)hipEventElapsedTime(&p.ms[span], p.ev[e0], p.ev[e1]);
+    return 0;
+}
+
 int rc_tree_build(immesh_ctx* c, const char* who, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int64_t* h_count, RcTree& t, int64_t n, const RcLeaves& src) {
     int rc;
     const size_t temp_bytes = std::max(rd_scan_temp_bytes(1, 1, std::max<int64_t>(n, 1)), sort_pairs_u64_temp_bytes((int)std::max<int64_t>(n, 1))) + 256;
@@ -105,13 +177,39 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
 
 }  // namespace
 
+// What a change of the caster's state discards.  A change of the snapshot is a build (rc_build: a rebuild, and the applies of a holes pass, a
+// simplification and a smoothing pass, which end in one) or the apply of an orientation, which keeps the hierarchy.  A new analysis replaces the old.
+//
+//   derived result                              | the snapshot changes  | a new analysis
+//   the last NEAREST cast, its reinforced points | discarded             | stay
+//   the samples (sm)                             | discarded             | stay
+//   the analysis (tp)                            | discarded             | replaced
+//   the orientation (ot), the holes pass (hl)    | discarded (they read the analysis) | discarded
+//   the simplification's result (sp)             | discarded             | stays
+//   the smoothing pass' result (so)              | discarded             | stays
+//   the closest-point results of the last query  | stay                  | stay
+//
+// The closest-point results stay readable on purpose: they are answers about the points of a query, not a view of the snapshot.  immesh_raycast
+// handles have_cast itself (a NEAREST cast replaces the last one, an ANY cast leaves it), and a pass clears its own `have` when it starts.  A new
+// derived result adds one line to one of these two functions and nowhere else.
+void rc_analysis_changed(immesh_raycaster* r) {
+    r->ot.have = false;   // an orientation belongs to the analysis whose half-edges it read
+    r->hl.have = false;   // and so does a holes pass
+}
+
+void rc_snapshot_changed(immesh_raycaster* r) {
+    r->have_cast = false; r->n_points = 0;
+    r->sm.have = false;
+    r->tp.have = false;
+    rc_analysis_changed(r);
+    r->sp.have = false;
+    r->so.have = false;
+}
+
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces) {
-    r->built = false; r->have_cast = false; r->n_points = 0;
-    r->sm.have = false;   // samples belong to the snapshot they were drawn from
-    r->tp.have = false;   // and so does the topology's analysis
-    r->sp.have = false;   // and a simplification's result
-    r->so.have = false;   // and a smoothing pass'
+    r->built = false;
+    rc_snapshot_changed(r);
     const RcLeaves src = {(const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p};
     const int rc = rc_tree_build(r->ctx, "raycast", r->s, r->ev[0], r->ev[1], r->h_small, r->tree, n_faces, src);
     if (rc) return rc;
@@ -205,14 +303,14 @@ int immesh_raycast(immesh_raycaster* r, const immesh_ray_frame* frame, const flo
                    int32_t mode, float* t_out, int32_t* face_out) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
-    if (!r->built) { c->err = "raycast: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    int rc = rc_built(r, "raycast");
+    if (rc) return rc;
     if (!frame) { c->err = "raycast: frame is NULL"; return IMMESH_E_INVAL; }
     if (n_rays < 0 || n_rays > (int64_t)0x7FFFFFFE || (n_rays > 0 && !dirs)) { c->err = "raycast: bad ray arrays"; return IMMESH_E_INVAL; }
     if (mode != IMMESH_RAY_NEAREST && mode != IMMESH_RAY_ANY) { c->err = "raycast: unknown mode " + std::to_string(mode); return IMMESH_E_INVAL; }
     if (!(t_min >= 0.0) || !(t_min < t_max) || !std::isfinite(t_max)) { c->err = "raycast: need 0 <= t_min < t_max, both finite"; return IMMESH_E_INVAL; }
     RcFrame fr;
-    int rc = rc_frame(c, "raycast", frame, &fr);
-    if (rc) return rc;
+    if ((rc = rc_frame(c, "raycast", frame, &fr))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     const int m = mode == IMMESH_RAY_NEAREST ? 0 : 1;   // an ANY cast leaves the last NEAREST cast's rays and distances where the reinforce pass reads them

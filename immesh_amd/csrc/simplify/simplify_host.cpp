@@ -7,7 +7,6 @@
 #include <cstddef>
 #include <cstring>
 #include <string>
-#include <utility>
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_simplify.h"
 #include "simplify.hpp"
@@ -22,29 +21,13 @@ static_assert(sizeof(immesh_simplify_stats) == 11 * 8 && offsetof(immesh_simplif
 
 namespace {
 
-enum { SS_VTX_IN = 0, SS_USED, SS_NOT_FINITE, SS_OUTSIDE, SS_VTX_OUT, SS_LARGEST, SS_FACES_IN, SS_NOT_COUNTING, SS_COLLAPSED, SS_DUPLICATE, SS_FACES_OUT };
 constexpr int64_t SP_MAX_VTX = 0x7FFFFFFE;                      // the sort's and the scan's int count
 
-int sp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, "simplify", b, bytes); }
-
-int sp_events(immesh_raycaster* r) {
-    immesh_ctx* c = r->ctx;
-    for (hipEvent_t& e : r->sp.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!r->sp.h_cnt) HIPCHK(c, hipHostMalloc((void**)&r->sp.h_cnt, SP_COUNTERS * 8));
-    return 0;
-}
+int sp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->sp, b, bytes); }
 
 int sp_passed(immesh_raycaster* r, const char* who) {
-    if (!r->built) { r->ctx->err = std::string(who) + ": no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
-    if (!r->sp.have) { r->ctx->err = std::string(who) + ": no simplify pass since the caster's last build or apply (immesh_simplify)"; return IMMESH_E_INVAL; }
-    return 0;
-}
-
-int sp_index_bits(int64_t n) {   // the bits the indices 0 .. n - 1 need
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
-    return bits;
+    const int rc = rc_built(r, who);
+    return rc ? rc : rc_passed(r, who, r->sp, "no simplify pass since the caster's last build or apply (immesh_simplify)");
 }
 
 }  // namespace
@@ -54,7 +37,8 @@ extern "C" {
 int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merge_duplicates, immesh_simplify_stats* stats) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
-    if (!r->built) { c->err = "simplify: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    int rc;
+    if ((rc = rc_built(r, "simplify"))) return rc;
     if (!(cell >= 0.0) || !std::isfinite(cell)) { c->err = "simplify: need 0 <= cell, finite"; return IMMESH_E_INVAL; }
     if (mode != IMMESH_SIMPLIFY_FIRST && mode != IMMESH_SIMPLIFY_MEAN) { c->err = "simplify: unknown mode " + std::to_string(mode); return IMMESH_E_INVAL; }
     const int64_t nv = r->n_vtx, nf = r->n_faces, ns = std::max(nv, nf);
@@ -62,10 +46,8 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     RcSimplify& o = r->sp;
-    int rc;
     o.have = false;
-    if ((rc = sp_events(r))) return rc;
-    if ((rc = sp_grow(r, o.cnt, SP_COUNTERS * 8))) return rc;
+    if ((rc = rc_pass_ready(r, "simplify", o, SP_COUNTERS, SP_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     const bool work = nf > 0 && nv > 0;
     if (work) {
@@ -88,8 +70,7 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
         const size_t temp = std::max({exclusive_sum_temp_bytes((int)ns), sort_pairs_u64_temp_bytes((int)ns), sort_pairs_u32_temp_bytes((int)ns)}) + 256;
         if ((rc = sp_grow(r, r->tree.temp, temp))) return rc;  // the caster's scan and sort scratch
     }
-    HIPCHK(c, hipEventRecord(o.ev[0], s));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, SP_COUNTERS * 8, s));
+    if ((rc = rc_pass_begin(r, o, 0))) return rc;
     if (work) {
         const float* vtx = (const float*)r->vtx.p;
         const int32_t* faces = (const int32_t*)r->faces.p;
@@ -129,7 +110,7 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
         unsigned long long* fk64 = (unsigned long long*)o.fk64.p;
         uint32_t* fk32 = (uint32_t*)o.fk32.p;
         if (merge_duplicates) {
-            const int bits = sp_index_bits(nv);                 // a new index is below n_vtx; the key that sets the others apart stays above in these bits too
+            const int bits = rc_index_bits(nv);                 // a new index is below n_vtx; the key that sets the others apart stays above in these bits too
             sp_launch_faces(s, faces, nf, nv, vmap, fstatus, keep, fk64, fk32, iota, cnt);
             sort_pairs_u32(s, temp, temp_bytes, fk32, k32s, iota, val_a, (int)nf, bits);
             sp_launch_gather64(s, fk64, val_a, nf, key_a);
@@ -141,20 +122,16 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
         exclusive_sum_i32(s, temp, temp_bytes, keep, koff, (int)nf);
         sp_launch_compact(s, faces, nf, vmap, keep, koff, (int32_t*)o.faces_out.p, (int32_t*)o.fmap.p, cnt);
     }
-    HIPCHK(c, hipEventRecord(o.ev[1], s));
-    unsigned long long* h = o.h_cnt;
-    HIPCHK(c, hipMemcpyAsync(h, cnt, SP_COUNTERS * 8, hipMemcpyDeviceToHost, s));   // the one read-back
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&o.ms[0], o.ev[0], o.ev[1]);
-    int64_t* st = o.st;
-    st[SS_VTX_IN] = nv; st[SS_USED] = (int64_t)h[SP_N_USED]; st[SS_NOT_FINITE] = (int64_t)h[SP_N_ALONE_NOT_FINITE];
-    st[SS_OUTSIDE] = (int64_t)h[SP_N_ALONE_OUTSIDE]; st[SS_VTX_OUT] = (int64_t)h[SP_N_CLUSTERS]; st[SS_LARGEST] = (int64_t)h[SP_LARGEST];
-    st[SS_FACES_IN] = nf; st[SS_NOT_COUNTING] = (int64_t)h[SP_N_NOT_COUNTING]; st[SS_COLLAPSED] = (int64_t)h[SP_N_COLLAPSED];
-    st[SS_DUPLICATE] = (int64_t)h[SP_N_DUPLICATE]; st[SS_FACES_OUT] = (int64_t)h[SP_N_FACES_OUT];
-    if (!work) st[SS_NOT_COUNTING] = nf;                        // (faces without a vertex to name: no build accepts them)
+    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, SP_COUNTERS))) return rc;   // the one read-back
+    const unsigned long long* h = o.h_cnt;
+    immesh_simplify_stats& st = o.st;
+    st.n_vertices_in = nv; st.n_vertices_used = (int64_t)h[SP_N_USED]; st.n_alone_not_finite = (int64_t)h[SP_N_ALONE_NOT_FINITE];
+    st.n_alone_outside = (int64_t)h[SP_N_ALONE_OUTSIDE]; st.n_vertices_out = (int64_t)h[SP_N_CLUSTERS]; st.largest_cluster = (int64_t)h[SP_LARGEST];
+    st.n_faces_in = nf; st.n_not_counting = (int64_t)h[SP_N_NOT_COUNTING]; st.n_collapsed = (int64_t)h[SP_N_COLLAPSED];
+    st.n_duplicate = (int64_t)h[SP_N_DUPLICATE]; st.n_faces_out = (int64_t)h[SP_N_FACES_OUT];
+    if (!work) st.n_not_counting = nf;                          // (faces without a vertex to name: no build accepts them)
     o.have = true;
-    if (stats) std::memcpy(stats, st, sizeof(*stats));
+    if (stats) *stats = st;
     return 0;
 }
 
@@ -163,20 +140,13 @@ int immesh_simplify_vertices(immesh_raycaster* r, float* vtx_out, int32_t* first
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = sp_passed(r, "simplify_vertices"))) return rc;
-    if (cap < 0) { c->err = "simplify_vertices: cap is negative"; return IMMESH_E_INVAL; }
     const RcSimplify& o = r->sp;
-    const int64_t n = o.st[SS_VTX_OUT];
-    if (n_out) *n_out = n;
-    if ((!vtx_out && !first_vertex && !n_members) || n == 0) return 0;
-    if (cap < n) {
-        c->err = "simplify_vertices: cap " + std::to_string(cap) + " < " + std::to_string(n) + " clusters";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = o.st.n_vertices_out;
+    if ((rc = rc_cap(c, "simplify_vertices", cap, n, n_out, vtx_out || first_vertex || n_members, "clusters"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if (vtx_out) HIPCHK(c, hipMemcpy(vtx_out, o.vtx_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
-    if (first_vertex) HIPCHK(c, hipMemcpy(first_vertex, o.first.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (n_members) HIPCHK(c, hipMemcpy(n_members, o.nmem.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_fetch(c, vtx_out, o.vtx_out.p, (size_t)n * 12))) return rc;
+    if ((rc = rc_fetch(c, first_vertex, o.first.p, (size_t)n * 4))) return rc;
+    return rc_fetch(c, n_members, o.nmem.p, (size_t)n * 4);
 }
 
 int immesh_simplify_maps(immesh_raycaster* r, int32_t* vmap, int32_t* fmap, int8_t* fstatus) {
@@ -193,10 +163,9 @@ int immesh_simplify_maps(immesh_raycaster* r, int32_t* vmap, int32_t* fmap, int8
         if (fstatus && nf > 0) std::memset(fstatus, IMMESH_FACE_NOT_COUNTING, (size_t)nf);
         return 0;
     }
-    if (vmap && nv > 0) HIPCHK(c, hipMemcpy(vmap, o.vmap.p, (size_t)nv * 4, hipMemcpyDeviceToHost));
-    if (fmap) HIPCHK(c, hipMemcpy(fmap, o.fmap.p, (size_t)nf * 4, hipMemcpyDeviceToHost));
-    if (fstatus) HIPCHK(c, hipMemcpy(fstatus, o.fstatus.p, (size_t)nf, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_fetch(c, vmap, o.vmap.p, (size_t)nv * 4))) return rc;
+    if ((rc = rc_fetch(c, fmap, o.fmap.p, (size_t)nf * 4))) return rc;
+    return rc_fetch(c, fstatus, o.fstatus.p, (size_t)nf);
 }
 
 int immesh_simplify_faces(immesh_raycaster* r, int32_t* faces_out, int64_t cap, int64_t* n_out) {
@@ -204,17 +173,10 @@ int immesh_simplify_faces(immesh_raycaster* r, int32_t* faces_out, int64_t cap, 
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = sp_passed(r, "simplify_faces"))) return rc;
-    if (cap < 0) { c->err = "simplify_faces: cap is negative"; return IMMESH_E_INVAL; }
-    const int64_t n = r->sp.st[SS_FACES_OUT];
-    if (n_out) *n_out = n;
-    if (!faces_out || n == 0) return 0;
-    if (cap < n) {
-        c->err = "simplify_faces: cap " + std::to_string(cap) + " < " + std::to_string(n) + " kept faces";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = r->sp.st.n_faces_out;
+    if ((rc = rc_cap(c, "simplify_faces", cap, n, n_out, faces_out != nullptr, "kept faces"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    HIPCHK(c, hipMemcpy(faces_out, r->sp.faces_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_fetch(c, faces_out, r->sp.faces_out.p, (size_t)n * 12);
 }
 
 int immesh_simplify_apply(immesh_raycaster* r) {
@@ -223,26 +185,16 @@ int immesh_simplify_apply(immesh_raycaster* r) {
     int rc;
     if ((rc = sp_passed(r, "simplify_apply"))) return rc;
     RcSimplify& o = r->sp;
-    const int64_t nv = o.st[SS_VTX_OUT], nf = o.st[SS_FACES_OUT];
+    const int64_t nv = o.st.n_vertices_out, nf = o.st.n_faces_out;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     HIPCHK(c, hipEventRecord(o.ev[2], s));
     if (nv > 0) {                                               // (zero clusters: nothing was launched and the result's buffers may not exist)
-        std::swap(r->vtx.p, o.vtx_out.p);                       // the stream is idle: the pass synchronised
-        std::swap(r->vtx.bytes, o.vtx_out.bytes);
-        std::swap(r->faces.p, o.faces_out.p);
-        std::swap(r->faces.bytes, o.faces_out.bytes);
+        rc_swap(r->vtx, o.vtx_out);                             // the stream is idle: the pass synchronised
+        rc_swap(r->faces, o.faces_out);
     }
-    o.have = false;
-    r->ot.have = false;
-    r->hl.have = false;
-    r->so.have = false;                                         // (the build discards a smoothing pass too)
-    rc = rc_build(r, nv, nf);                                   // discards the last cast, the samples and the analysis; the stream is idle on return
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(o.ev[3], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&o.ms[1], o.ev[2], o.ev[3]);
-    return 0;
+    if ((rc = rc_build(r, nv, nf))) return rc;                  // discards what read the snapshot, this pass too; the stream is idle on return
+    return rc_pass_span(r, o, 2, 3, 1);
 }
 
 int immesh_simplify_last_timing(immesh_raycaster* r, float* ms) {

@@ -14,12 +14,7 @@ enum {
 enum { SM_FLAG_BORDER = 0, SM_FLAG_MOVING = 1, SM_FLAGS = 2 };
 
 // The pair key of a directed edge is (u << 32) | v: row u, neighbour v.  A face that does not count emits six times the key (n_vtx << 32), above
-// every real one, so the sort needs 32 + sm_index_bits(n_vtx + 1) bits and the rows end where that run begins.
-inline int sm_index_bits(int64_t n) {   // the bits the values 0 .. n - 1 need
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
-    return bits;
-}
+// every real one, so the sort needs 32 + rc_index_bits(n_vtx + 1) bits and the rows end where that run begins.
 
 // ---- the one-ring ----------------------------------------------------------------------------------------------------------------------------------------
 // one lane per face: key[6 f .. 6 f + 5] = its six directed pairs, val[6 f + e] = 6 f + e (the sort's values; nothing reads them)

@@ -7,7 +7,6 @@
 #include <cstddef>
 #include <cstring>
 #include <string>
-#include <utility>
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_smooth.h"
 #include "smooth.hpp"
@@ -22,23 +21,9 @@ static_assert(sizeof(immesh_smooth_stats) == 12 * 8 && offsetof(immesh_smooth_st
 
 namespace {
 
-enum { MS_VERTICES = 0, MS_USED, MS_NOT_FINITE, MS_BORDER, MS_INTERIOR, MS_MOVING, MS_PAIRS, MS_VALENCE, MS_STEPS, MS_HELD, MS_MOVED };
 constexpr int64_t SM_MAX_COUNT = 0x7FFFFFFE;                    // the sort's and the scan's int count
 
-int sm_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, "smooth", b, bytes); }
-
-int sm_events(immesh_raycaster* r) {
-    immesh_ctx* c = r->ctx;
-    for (hipEvent_t& e : r->so.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!r->so.h_cnt) HIPCHK(c, hipHostMalloc((void**)&r->so.h_cnt, SM_COUNTERS * 8));
-    return 0;
-}
-
-int sm_built(immesh_raycaster* r, const char* who) {
-    if (!r->built) { r->ctx->err = std::string(who) + ": no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
-    return 0;
-}
+int sm_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->so, b, bytes); }
 
 int sm_sizes(immesh_raycaster* r, const char* who) {
     if (6 * r->n_faces > SM_MAX_COUNT) { r->ctx->err = std::string(who) + ": more than 2^31 - 2 directed pairs (6 x " + std::to_string(r->n_faces) + " faces)"; return IMMESH_E_INVAL; }
@@ -47,10 +32,8 @@ int sm_sizes(immesh_raycaster* r, const char* who) {
 }
 
 int sm_passed(immesh_raycaster* r, const char* who) {
-    int rc;
-    if ((rc = sm_built(r, who))) return rc;
-    if (!r->so.have) { r->ctx->err = std::string(who) + ": no smooth pass since the caster's last build or apply (immesh_smooth)"; return IMMESH_E_INVAL; }
-    return 0;
+    const int rc = rc_built(r, who);
+    return rc ? rc : rc_passed(r, who, r->so, "no smooth pass since the caster's last build or apply (immesh_smooth)");
 }
 
 }  // namespace
@@ -61,7 +44,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = sm_built(r, "smooth"))) return rc;
+    if ((rc = rc_built(r, "smooth"))) return rc;
     if (n_steps < 0 || n_steps > IMMESH_SMOOTH_MAX_STEPS) { c->err = "smooth: need 0 <= n_steps <= 65536, got " + std::to_string(n_steps); return IMMESH_E_INVAL; }
     if (!std::isfinite(lambda) || !std::isfinite(mu) || lambda < -1.0 || lambda > 1.0 || mu < -1.0 || mu > 1.0) {
         c->err = "smooth: need lambda and mu finite and in [-1, 1]";
@@ -77,8 +60,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
     hipStream_t s = r->s;
     RcSmooth& o = r->so;
     o.have = false;
-    if ((rc = sm_events(r))) return rc;
-    if ((rc = sm_grow(r, o.cnt, SM_COUNTERS * 8))) return rc;
+    if ((rc = rc_pass_ready(r, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     const bool ring = nf > 0 && nv > 0;
     if (nv > 0) {
@@ -99,8 +81,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         if ((rc = sm_grow(r, r->tree.temp, temp))) return rc;   // the caster's scan and sort scratch
     }
     const float* vtx = (const float*)r->vtx.p;
-    HIPCHK(c, hipEventRecord(o.ev[0], s));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, SM_COUNTERS * 8, s));
+    if ((rc = rc_pass_begin(r, o, 0))) return rc;
     if (nv > 0) {
         HIPCHK(c, hipMemsetAsync(o.flag.p, 0, (size_t)nv * SM_FLAGS, s));
         if (!ring) {                                            // no face: every vertex is unused and every row empty
@@ -115,7 +96,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         int32_t *rstart = (int32_t*)o.rstart.p, *neighbours = (int32_t*)o.neighbours.p, *uses = (int32_t*)o.uses.p;
         int8_t *flag = (int8_t*)o.flag.p, *vclass = (int8_t*)o.vclass.p;
         sm_launch_emit(s, (const int32_t*)r->faces.p, nf, nv, key_a, (int32_t*)o.val_a.p);
-        sort_pairs_u64(s, temp, temp_bytes, key_a, key_b, (const int32_t*)o.val_a.p, (int32_t*)o.val_b.p, (int)n6, 32 + sm_index_bits(nv + 1));
+        sort_pairs_u64(s, temp, temp_bytes, key_a, key_b, (const int32_t*)o.val_a.p, (int32_t*)o.val_b.p, (int)n6, 32 + rc_index_bits(nv + 1));
         int32_t *head = (int32_t*)key_a, *scan = head + n6;     // the unsorted keys are done with: the heads and their scan lie in them
         sm_launch_heads(s, key_b, n6, head);
         exclusive_sum_i32(s, temp, temp_bytes, head, scan, (int)n6);
@@ -141,23 +122,16 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         }
         sm_launch_finish(s, vtx, (const float*)o.pos[o.cur].p, nv, (const int8_t*)o.flag.p, cnt);
     }
-    HIPCHK(c, hipEventRecord(o.ev[3], s));
-    unsigned long long* h = o.h_cnt;
-    HIPCHK(c, hipMemcpyAsync(h, cnt, SM_COUNTERS * 8, hipMemcpyDeviceToHost, s));   // the one read-back
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = rc_pass_end(r, o, 2, 3, 1, 0, SM_COUNTERS))) return rc;   // the one read-back; it ends both spans
     (void)hipEventElapsedTime(&o.ms[0], o.ev[0], o.ev[1]);
-    (void)hipEventElapsedTime(&o.ms[1], o.ev[2], o.ev[3]);
-    int64_t* st = o.st;
-    st[MS_VERTICES] = nv; st[MS_USED] = (int64_t)h[SM_N_USED]; st[MS_NOT_FINITE] = (int64_t)h[SM_N_NOT_FINITE]; st[MS_BORDER] = (int64_t)h[SM_N_BORDER];
-    st[MS_INTERIOR] = (int64_t)h[SM_N_INTERIOR]; st[MS_MOVING] = (int64_t)h[SM_N_MOVING]; st[MS_PAIRS] = (int64_t)h[SM_N_PAIRS];
-    st[MS_VALENCE] = (int64_t)h[SM_MAX_VALENCE]; st[MS_STEPS] = n_steps; st[MS_HELD] = (int64_t)h[SM_N_HELD]; st[MS_MOVED] = (int64_t)h[SM_N_MOVED];
-    std::memcpy(&o.max_disp2, &h[SM_MAX_DISP2], 8);
+    const unsigned long long* h = o.h_cnt;
+    immesh_smooth_stats& st = o.st;
+    st.n_vertices = nv; st.n_used = (int64_t)h[SM_N_USED]; st.n_not_finite = (int64_t)h[SM_N_NOT_FINITE]; st.n_border = (int64_t)h[SM_N_BORDER];
+    st.n_interior = (int64_t)h[SM_N_INTERIOR]; st.n_moving = (int64_t)h[SM_N_MOVING]; st.n_pairs = (int64_t)h[SM_N_PAIRS];
+    st.max_valence = (int64_t)h[SM_MAX_VALENCE]; st.n_steps = n_steps; st.n_held = (int64_t)h[SM_N_HELD]; st.n_moved = (int64_t)h[SM_N_MOVED];
+    std::memcpy(&st.max_disp2, &h[SM_MAX_DISP2], 8);
     o.have = true;
-    if (stats) {
-        std::memcpy(stats, st, sizeof(o.st));
-        stats->max_disp2 = o.max_disp2;
-    }
+    if (stats) *stats = st;
     return 0;
 }
 
@@ -170,9 +144,8 @@ int immesh_smooth_vertices(immesh_raycaster* r, float* vtx_out, int8_t* vclass) 
     const int64_t nv = r->n_vtx;
     if (nv == 0) return 0;
     (void)hipSetDevice(c->cfg.device);
-    if (vtx_out) HIPCHK(c, hipMemcpy(vtx_out, o.pos[o.cur].p, (size_t)nv * 12, hipMemcpyDeviceToHost));
-    if (vclass) HIPCHK(c, hipMemcpy(vclass, o.vclass.p, (size_t)nv, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_fetch(c, vtx_out, o.pos[o.cur].p, (size_t)nv * 12))) return rc;
+    return rc_fetch(c, vclass, o.vclass.p, (size_t)nv);
 }
 
 int immesh_smooth_adjacency(immesh_raycaster* r, int64_t* row_start, int32_t* neighbours, int32_t* uses, int64_t cap, int64_t* n_out) {
@@ -180,23 +153,14 @@ int immesh_smooth_adjacency(immesh_raycaster* r, int64_t* row_start, int32_t* ne
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = sm_passed(r, "smooth_adjacency"))) return rc;
-    if (cap < 0) { c->err = "smooth_adjacency: cap is negative"; return IMMESH_E_INVAL; }
     const RcSmooth& o = r->so;
-    const int64_t n = o.st[MS_PAIRS], nv = r->n_vtx;
-    if (n_out) *n_out = n;
-    if (!row_start && !neighbours && !uses) return 0;
-    if (cap < n) {
-        c->err = "smooth_adjacency: cap " + std::to_string(cap) + " < " + std::to_string(n) + " entries";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = o.st.n_pairs, nv = r->n_vtx;
+    if ((rc = rc_cap(c, "smooth_adjacency", cap, n, n_out, row_start || neighbours || uses, "entries"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if (row_start) {
-        if (nv > 0) HIPCHK(c, hipMemcpy(row_start, o.row_start.p, (size_t)(nv + 1) * 8, hipMemcpyDeviceToHost));
-        else row_start[0] = 0;
-    }
-    if (neighbours && n > 0) HIPCHK(c, hipMemcpy(neighbours, o.neighbours.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (uses && n > 0) HIPCHK(c, hipMemcpy(uses, o.uses.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
+    if (row_start && nv == 0) row_start[0] = 0;
+    else if ((rc = rc_fetch(c, row_start, o.row_start.p, (size_t)(nv + 1) * 8))) return rc;
+    if ((rc = rc_fetch(c, neighbours, o.neighbours.p, (size_t)n * 4))) return rc;
+    return rc_fetch(c, uses, o.uses.p, (size_t)n * 4);
 }
 
 int immesh_smooth_apply(immesh_raycaster* r) {
@@ -210,18 +174,10 @@ int immesh_smooth_apply(immesh_raycaster* r) {
     hipStream_t s = r->s;
     HIPCHK(c, hipEventRecord(o.ev[4], s));
     if (nv > 0) {                                               // (no vertex: nothing was launched and the result's buffers may not exist)
-        std::swap(r->vtx.p, o.pos[o.cur].p);                    // the stream is idle: the pass synchronised
-        std::swap(r->vtx.bytes, o.pos[o.cur].bytes);
+        rc_swap(r->vtx, o.pos[o.cur]);                          // the stream is idle: the pass synchronised
     }
-    o.have = false;
-    r->ot.have = false;
-    r->hl.have = false;
-    rc = rc_build(r, nv, nf);                                   // discards the last cast, the samples, the analysis and a simplification; the stream is idle on return
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(o.ev[5], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&o.ms[2], o.ev[4], o.ev[5]);
-    return 0;
+    if ((rc = rc_build(r, nv, nf))) return rc;                  // discards what read the snapshot, this pass too; the stream is idle on return
+    return rc_pass_span(r, o, 4, 5, 2);
 }
 
 int immesh_smooth_last_timing(immesh_raycaster* r, float* ms) {
@@ -234,7 +190,7 @@ int immesh_vertex_normals(immesh_raycaster* r, float* normals_out, int64_t* n_ze
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = sm_built(r, "vertex_normals"))) return rc;
+    if ((rc = rc_built(r, "vertex_normals"))) return rc;
     if ((rc = sm_sizes(r, "vertex_normals"))) return rc;
     const int64_t nv = r->n_vtx, nf = r->n_faces, n3 = 3 * nf;
     if (n_zero) *n_zero = 0;
@@ -242,8 +198,7 @@ int immesh_vertex_normals(immesh_raycaster* r, float* normals_out, int64_t* n_ze
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     RcSmooth& o = r->so;
-    if ((rc = sm_events(r))) return rc;
-    if ((rc = sm_grow(r, o.cnt, SM_COUNTERS * 8))) return rc;
+    if ((rc = rc_pass_ready(r, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
     if ((rc = sm_grow(r, o.normals, (size_t)nv * 12))) return rc;
     if (nf > 0) {
         RcBuf* const per_corner[] = {&o.nkey_a, &o.nkey_b, &o.nval_a, &o.nval_b};
@@ -256,7 +211,7 @@ int immesh_vertex_normals(immesh_raycaster* r, float* normals_out, int64_t* n_ze
     if (nf > 0) {
         sm_launch_incidence(s, (const float*)r->vtx.p, nv, (const int32_t*)r->faces.p, nf, (uint32_t*)o.nkey_a.p, (int32_t*)o.nval_a.p);
         sort_pairs_u32(s, r->tree.temp.p, r->tree.temp.bytes, (const uint32_t*)o.nkey_a.p, (uint32_t*)o.nkey_b.p, (const int32_t*)o.nval_a.p, (int32_t*)o.nval_b.p,
-                       (int)n3, sm_index_bits(nv + 1));         // stable: the faces of a vertex stay in ascending order
+                       (int)n3, rc_index_bits(nv + 1));         // stable: the faces of a vertex stay in ascending order
     }
     sm_launch_normals(s, (const float*)r->vtx.p, nv, (const int32_t*)r->faces.p, nf, (const uint32_t*)o.nkey_b.p, (const int32_t*)o.nval_b.p, (float*)o.normals.p,
                       cnt);
@@ -264,8 +219,7 @@ int immesh_vertex_normals(immesh_raycaster* r, float* normals_out, int64_t* n_ze
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     if (n_zero) *n_zero = (int64_t)o.h_cnt[SM_N_ZERO];
-    if (normals_out) HIPCHK(c, hipMemcpy(normals_out, o.normals.p, (size_t)nv * 12, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_fetch(c, normals_out, o.normals.p, (size_t)nv * 12);
 }
 
 }  // extern "C"

@@ -7,8 +7,6 @@
 #include <cmath>
 #include <cstddef>
 #include <string>
-#include <utility>
-#include <vector>
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_topology.h"
 #include "topology.hpp"
@@ -24,35 +22,15 @@ static_assert(sizeof(HlRank) == 8, "HlRank layout");
 
 namespace {
 
-enum { HS_LOOPS = 0, HS_SIMPLE, HS_NONSIMPLE, HS_OUTLINE, HS_TOO_LONG, HS_TOO_WIDE, HS_BLOCKED, HS_FILLED, HS_NEW, HS_CLOSED, HS_LARGEST, HS_CYCLE };
-constexpr size_t TP_ST_BOUNDARY = offsetof(immesh_topology_stats, n_boundary) / 8;          // their places in RcTopology::st
-constexpr size_t TP_ST_LOOPS = offsetof(immesh_topology_stats, n_boundary_loops) / 8;
-constexpr size_t TP_ST_LARGEST_LOOP = offsetof(immesh_topology_stats, largest_loop_edges) / 8;
 constexpr int64_t HL_MAX_VTX = 0x7FFFFFFF;                      // the scan's int count
 constexpr int64_t HL_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;   // what a build takes
 constexpr int64_t HL_MAX_ANALYSED = ((int64_t)0x7FFFFFFE) / 3;  // what an analysis takes
 
-int hl_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, "topology_holes", b, bytes); }
-
-int hl_events(immesh_raycaster* r) {
-    immesh_ctx* c = r->ctx;
-    for (hipEvent_t& e : r->hl.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!r->hl.h_cnt) HIPCHK(c, hipHostMalloc((void**)&r->hl.h_cnt, HC_COUNTERS * 8));
-    return 0;
-}
-
-int hl_analysed(immesh_raycaster* r, const char* who) {
-    if (!r->built) { r->ctx->err = std::string(who) + ": no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
-    if (!r->tp.have) { r->ctx->err = std::string(who) + ": no analysis since the caster's last build (immesh_topology_analyse)"; return IMMESH_E_INVAL; }
-    return 0;
-}
+int hl_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->hl, b, bytes); }
 
 int hl_passed(immesh_raycaster* r, const char* who) {
-    const int rc = hl_analysed(r, who);
-    if (rc) return rc;
-    if (!r->hl.have) { r->ctx->err = std::string(who) + ": no holes pass since the last analysis (immesh_topology_holes)"; return IMMESH_E_INVAL; }
-    return 0;
+    const int rc = rc_analysed(r, who);
+    return rc ? rc : rc_passed(r, who, r->hl, "no holes pass since the last analysis (immesh_topology_holes)");
 }
 
 }  // namespace
@@ -63,7 +41,7 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = hl_analysed(r, "topology_holes"))) return rc;
+    if ((rc = rc_analysed(r, "topology_holes"))) return rc;
     if (max_edges < 3) { c->err = "topology_holes: max_edges " + std::to_string(max_edges) + " is below 3"; return IMMESH_E_INVAL; }
     if (!(max_diagonal >= 0.0) || !std::isfinite(max_diagonal)) { c->err = "topology_holes: need 0 <= max_diagonal, finite"; return IMMESH_E_INVAL; }
     if (r->n_vtx > HL_MAX_VTX) { c->err = "topology_holes: more than 2^31 - 1 vertices (" + std::to_string(r->n_vtx) + ")"; return IMMESH_E_INVAL; }
@@ -71,10 +49,9 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
     hipStream_t s = r->s;
     const RcTopology& q = r->tp;
     RcHoles& o = r->hl;
-    const int64_t nv = r->n_vtx, n_half = q.n_half, n_loops = q.st[TP_ST_LOOPS], n_room = q.st[TP_ST_BOUNDARY], largest = q.st[TP_ST_LARGEST_LOOP];
+    const int64_t nv = r->n_vtx, n_half = q.n_half, n_loops = q.st.n_boundary_loops, n_room = q.st.n_boundary, largest = q.st.largest_loop_edges;
     o.have = false;
-    if ((rc = hl_events(r))) return rc;
-    if ((rc = hl_grow(r, o.cnt, HC_COUNTERS * 8))) return rc;
+    if ((rc = rc_pass_ready(r, "topology_holes", o, HC_COUNTERS, HC_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     if (n_loops > 0) {
         if ((rc = hl_grow(r, o.vt, (size_t)nv * HV_TABLES * 4))) return rc;
@@ -89,8 +66,7 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
         if ((rc = hl_grow(r, o.new_loop, (size_t)n_room * 4))) return rc;
         if ((rc = hl_grow(r, r->tree.temp, exclusive_sum_temp_bytes((int)std::max(nv, n_loops)) + 256))) return rc;   // the caster's scan scratch
     }
-    HIPCHK(c, hipEventRecord(o.ev[0], s));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, HC_COUNTERS * 8, s));
+    if ((rc = rc_pass_begin(r, o, 0))) return rc;
     if (n_loops > 0) {
         const unsigned long long* key = (const unsigned long long*)q.key_b.p;
         int32_t *vt = (int32_t*)o.vt.p, *lt = (int32_t*)o.lt.p, *cycle = (int32_t*)o.cycle.p, *cloop = (int32_t*)o.cloop.p;
@@ -113,20 +89,16 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
         exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, lt + HL_FILL * n_loops, lt + HL_FOFF * n_loops, (int)n_loops);
         hl_launch_emit(s, n_room, cycle, cloop, lt, n_loops, (int32_t*)o.new_faces.p, (int32_t*)o.new_loop.p, cnt);
     }
-    HIPCHK(c, hipEventRecord(o.ev[1], s));
-    unsigned long long* h = o.h_cnt;
-    HIPCHK(c, hipMemcpyAsync(h, cnt, HC_COUNTERS * 8, hipMemcpyDeviceToHost, s));   // the one read-back
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&o.ms[0], o.ev[0], o.ev[1]);
-    int64_t* st = o.st;
-    st[HS_LOOPS] = n_loops; st[HS_SIMPLE] = (int64_t)h[HC_N_SIMPLE]; st[HS_NONSIMPLE] = (int64_t)h[HC_N_NONSIMPLE];
-    st[HS_OUTLINE] = (int64_t)h[HC_N_OUTLINE]; st[HS_TOO_LONG] = (int64_t)h[HC_N_TOO_LONG]; st[HS_TOO_WIDE] = (int64_t)h[HC_N_TOO_WIDE];
-    st[HS_BLOCKED] = (int64_t)h[HC_N_BLOCKED]; st[HS_FILLED] = (int64_t)h[HC_N_FILLED]; st[HS_NEW] = (int64_t)h[HC_N_NEW];
-    st[HS_CLOSED] = (int64_t)h[HC_N_CLOSED]; st[HS_LARGEST] = (int64_t)h[HC_LARGEST_SIMPLE]; st[HS_CYCLE] = (int64_t)h[HC_N_CYCLE];
+    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, HC_COUNTERS))) return rc;   // the one read-back
+    const unsigned long long* h = o.h_cnt;
+    immesh_holes_stats& st = o.st;
+    st.n_loops = n_loops; st.n_simple = (int64_t)h[HC_N_SIMPLE]; st.n_nonsimple = (int64_t)h[HC_N_NONSIMPLE];
+    st.n_outline = (int64_t)h[HC_N_OUTLINE]; st.n_too_long = (int64_t)h[HC_N_TOO_LONG]; st.n_too_wide = (int64_t)h[HC_N_TOO_WIDE];
+    st.n_blocked = (int64_t)h[HC_N_BLOCKED]; st.n_filled = (int64_t)h[HC_N_FILLED]; st.n_new_faces = (int64_t)h[HC_N_NEW];
+    st.n_edges_closed = (int64_t)h[HC_N_CLOSED]; st.largest_simple_loop_edges = (int64_t)h[HC_LARGEST_SIMPLE]; st.n_cycle_vertices = (int64_t)h[HC_N_CYCLE];
     o.n_loops = n_loops;
     o.have = true;
-    if (stats) std::memcpy(stats, st, sizeof(*stats));
+    if (stats) *stats = st;
     return 0;
 }
 
@@ -136,28 +108,19 @@ int immesh_topology_holes_loops(immesh_raycaster* r, int32_t* first_vertex, int3
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = hl_passed(r, "topology_holes_loops"))) return rc;
-    if (cap < 0) { c->err = "topology_holes_loops: cap is negative"; return IMMESH_E_INVAL; }
     const RcHoles& o = r->hl;
     const int64_t n = o.n_loops;
-    if (n_out) *n_out = n;
-    if ((!first_vertex && !n_edges && !status && !box && !cycle_start) || n == 0) return 0;
-    if (cap < n) {
-        c->err = "topology_holes_loops: cap " + std::to_string(cap) + " < " + std::to_string(n) + " loops";
-        return IMMESH_E_CAPACITY;
-    }
+    const bool wanted = first_vertex || n_edges || status || box || cycle_start;
+    if ((rc = rc_cap(c, "topology_holes_loops", cap, n, n_out, wanted, "loops"))) return rc;
+    if (!wanted || n == 0) return 0;
     (void)hipSetDevice(c->cfg.device);
     const int32_t* lt = (const int32_t*)o.lt.p;
     int32_t* const out[3] = {first_vertex, n_edges, status};
     const int which[3] = {HL_FIRST, HL_NEDGES, HL_STATUS};
     for (int k = 0; k < 3; k++)
-        if (out[k]) HIPCHK(c, hipMemcpy(out[k], lt + which[k] * n, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (box) {
-        std::vector<uint32_t> keys((size_t)n * 6);
-        HIPCHK(c, hipMemcpy(keys.data(), o.box.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < 6 * n; i++) box[i] = tp_unkey_host(keys[(size_t)i], i % 6 < 3);
-    }
-    if (cycle_start) HIPCHK(c, hipMemcpy(cycle_start, o.cstart.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return 0;
+        if ((rc = rc_fetch(c, out[k], lt + which[k] * n, (size_t)n * 4))) return rc;
+    if (box && (rc = tp_fetch_boxes(c, box, o.box, n))) return rc;
+    return rc_fetch(c, cycle_start, o.cstart.p, (size_t)n * 8);
 }
 
 int immesh_topology_holes_cycles(immesh_raycaster* r, int32_t* cycle_out, int64_t cap, int64_t* n_out) {
@@ -165,17 +128,10 @@ int immesh_topology_holes_cycles(immesh_raycaster* r, int32_t* cycle_out, int64_
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = hl_passed(r, "topology_holes_cycles"))) return rc;
-    if (cap < 0) { c->err = "topology_holes_cycles: cap is negative"; return IMMESH_E_INVAL; }
-    const int64_t n = r->hl.st[HS_CYCLE];
-    if (n_out) *n_out = n;
-    if (!cycle_out || n == 0) return 0;
-    if (cap < n) {
-        c->err = "topology_holes_cycles: cap " + std::to_string(cap) + " < " + std::to_string(n) + " cycle vertices";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = r->hl.st.n_cycle_vertices;
+    if ((rc = rc_cap(c, "topology_holes_cycles", cap, n, n_out, cycle_out != nullptr, "cycle vertices"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    HIPCHK(c, hipMemcpy(cycle_out, r->hl.cycle.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_fetch(c, cycle_out, r->hl.cycle.p, (size_t)n * 4);
 }
 
 int immesh_topology_holes_faces(immesh_raycaster* r, int32_t* loop_out, int32_t* faces_out, int64_t cap, int64_t* n_out) {
@@ -183,18 +139,11 @@ int immesh_topology_holes_faces(immesh_raycaster* r, int32_t* loop_out, int32_t*
     immesh_ctx* c = r->ctx;
     int rc;
     if ((rc = hl_passed(r, "topology_holes_faces"))) return rc;
-    if (cap < 0) { c->err = "topology_holes_faces: cap is negative"; return IMMESH_E_INVAL; }
-    const int64_t n = r->hl.st[HS_NEW];
-    if (n_out) *n_out = n;
-    if ((!loop_out && !faces_out) || n == 0) return 0;
-    if (cap < n) {
-        c->err = "topology_holes_faces: cap " + std::to_string(cap) + " < " + std::to_string(n) + " new faces";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = r->hl.st.n_new_faces;
+    if ((rc = rc_cap(c, "topology_holes_faces", cap, n, n_out, loop_out || faces_out, "new faces"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if (loop_out) HIPCHK(c, hipMemcpy(loop_out, r->hl.new_loop.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (faces_out) HIPCHK(c, hipMemcpy(faces_out, r->hl.new_faces.p, (size_t)n * 12, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_fetch(c, loop_out, r->hl.new_loop.p, (size_t)n * 4))) return rc;
+    return rc_fetch(c, faces_out, r->hl.new_faces.p, (size_t)n * 12);
 }
 
 int immesh_topology_holes_apply(immesh_raycaster* r) {
@@ -203,7 +152,7 @@ int immesh_topology_holes_apply(immesh_raycaster* r) {
     int rc;
     if ((rc = hl_passed(r, "topology_holes_apply"))) return rc;
     RcHoles& o = r->hl;
-    const int64_t nf = r->n_faces, n_new = o.st[HS_NEW], total = nf + n_new;
+    const int64_t nf = r->n_faces, n_new = o.st.n_new_faces, total = nf + n_new;
     if (total > HL_MAX_FACES || total > HL_MAX_ANALYSED) {
         c->err = "topology_holes_apply: " + std::to_string(nf) + " faces and " + std::to_string(n_new) + " new ones exceed 2^30 faces or 2^31 - 2 half-edges";
         return IMMESH_E_INVAL;
@@ -214,18 +163,9 @@ int immesh_topology_holes_apply(immesh_raycaster* r) {
     HIPCHK(c, hipEventRecord(o.ev[2], s));
     if (nf > 0) HIPCHK(c, hipMemcpyAsync(o.merged.p, r->faces.p, (size_t)nf * 12, hipMemcpyDeviceToDevice, s));
     if (n_new > 0) HIPCHK(c, hipMemcpyAsync((int32_t*)o.merged.p + 3 * nf, o.new_faces.p, (size_t)n_new * 12, hipMemcpyDeviceToDevice, s));
-    std::swap(r->faces.p, o.merged.p);                          // the stream runs in order: the copies are queued before the build reads them
-    std::swap(r->faces.bytes, o.merged.bytes);
-    o.have = false;
-    r->ot.have = false;
-    r->sp.have = false;                                         // (the build discards it too: the faces changed)
-    r->so.have = false;                                         // (and a smoothing pass)
-    rc = rc_build(r, r->n_vtx, total);                          // discards the last cast, the samples and the analysis; the stream is idle on return
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(o.ev[3], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&o.ms[1], o.ev[2], o.ev[3]);
-    return 0;
+    rc_swap(r->faces, o.merged);                                // the stream runs in order: the copies are queued before the build reads them
+    if ((rc = rc_build(r, r->n_vtx, total))) return rc;         // discards what read the snapshot, this pass too; the stream is idle on return
+    return rc_pass_span(r, o, 2, 3, 1);
 }
 
 int immesh_topology_holes_last_timing(immesh_raycaster* r, float* ms) {

@@ -22,6 +22,8 @@ inline float tp_unkey_host(uint32_t k, bool lo) {
     std::memcpy(&f, &u, 4);
     return f;
 }
+// box[6 i] = the floats of n boxes' keys on the device (lo xyz, hi xyz): the components' and the loops' (topology_host.cpp)
+int tp_fetch_boxes(immesh_ctx* c, float* box, const RcBuf& keys, int64_t n);
 
 // analyse ---------------------------------------------------------------------------------------------------------------------------------
 // flag[f] = 1 for a counting face (three pairwise different indices in [0, n_vtx)), parent[f] = f, used[v] = 1 for its vertices (used zeroed by the caller)

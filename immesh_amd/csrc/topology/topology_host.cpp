@@ -21,18 +21,8 @@ static_assert(sizeof(immesh_topology_stats) == 14 * 8 && offsetof(immesh_topolog
 namespace {
 
 constexpr int64_t TP_MAX_FACES = ((int64_t)0x7FFFFFFE) / 3;   // 3 n_faces <= 2^31 - 2: the sort's int count, the half-edge id
-enum { ST_FACES = 0, ST_COUNTING, ST_DEGENERATE, ST_VERTICES, ST_EDGES, ST_BOUNDARY, ST_INTERIOR, ST_NONMANIFOLD, ST_INCONSISTENT, ST_COMPONENTS, ST_LARGEST,
-       ST_LOOPS, ST_LARGEST_LOOP, ST_EULER };
 
-int tp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, "topology", b, bytes); }
-
-int tp_events(immesh_raycaster* r) {
-    immesh_ctx* c = r->ctx;
-    for (hipEvent_t& e : r->tp.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!r->tp.h_cnt) HIPCHK(c, hipHostMalloc((void**)&r->tp.h_cnt, (TP_COUNTERS + 2) * 8));
-    return 0;
-}
+int tp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->tp, b, bytes); }
 
 // scan and sort scratch: the caster's (the reinforce pass and the sampler share it too)
 int tp_temp(immesh_raycaster* r, int64_t n_scan, int64_t n_sort) {
@@ -40,19 +30,14 @@ int tp_temp(immesh_raycaster* r, int64_t n_scan, int64_t n_sort) {
     return tp_grow(r, r->tree.temp, need);
 }
 
-int tp_analysed(immesh_raycaster* r, const char* who) {
-    if (!r->built) { r->ctx->err = std::string(who) + ": no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
-    if (!r->tp.have) { r->ctx->err = std::string(who) + ": no analysis since the caster's last build (immesh_topology_analyse)"; return IMMESH_E_INVAL; }
+}  // namespace
+
+int tp_fetch_boxes(immesh_ctx* c, float* box, const RcBuf& keys, int64_t n) {
+    std::vector<uint32_t> k((size_t)n * 6);
+    HIPCHK(c, hipMemcpy(k.data(), keys.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < 6 * n; i++) box[i] = tp_unkey_host(k[(size_t)i], i % 6 < 3);
     return 0;
 }
-
-int tp_key_bits(int64_t n_vtx) {   // the bits the indices 0 .. n_vtx - 1 need
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < n_vtx) bits++;
-    return bits;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -60,17 +45,15 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     RcTopology& q = r->tp;
-    if (!r->built) { c->err = "topology_analyse: no hierarchy has been built (immesh_raycast_build_triangles / _build_mesh)"; return IMMESH_E_INVAL; }
+    int rc;
+    if ((rc = rc_built(r, "topology_analyse"))) return rc;
     const int64_t nf = r->n_faces, nv = r->n_vtx;
     if (nf > TP_MAX_FACES) { c->err = "topology_analyse: 3 n_faces exceeds 2^31 - 2 (" + std::to_string(nf) + " faces)"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
-    int rc;
     q.have = false;
-    r->ot.have = false;   // an orientation belongs to the analysis whose half-edges it read
-    r->hl.have = false;   // and so does a holes pass
-    if ((rc = tp_events(r))) return rc;
-    if ((rc = tp_grow(r, q.cnt, TP_COUNTERS * 8))) return rc;
+    rc_analysis_changed(r);
+    if ((rc = rc_pass_ready(r, "topology", q, TP_COUNTERS, TP_COUNTERS + 2))) return rc;
     if ((rc = tp_grow(r, q.flag, (size_t)nf * 4))) return rc;
     if ((rc = tp_grow(r, q.off, (size_t)nf * 4))) return rc;
     if ((rc = tp_grow(r, q.parent, (size_t)nf * 4))) return rc;
@@ -86,8 +69,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
     int32_t *flag = (int32_t*)q.flag.p, *off = (int32_t*)q.off.p, *parent = (int32_t*)q.parent.p, *vparent = (int32_t*)q.vparent.p;
     unsigned long long* cnt = (unsigned long long*)q.cnt.p;
     unsigned long long* h = q.h_cnt;
-    HIPCHK(c, hipEventRecord(q.ev[0], s));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, TP_COUNTERS * 8, s));
+    if ((rc = rc_pass_begin(r, q, 0))) return rc;
     int64_t n_counting = 0;
     if (nf > 0) {
         if (nv > 0) HIPCHK(c, hipMemsetAsync(q.used.p, 0, (size_t)nv * 4, s));
@@ -114,7 +96,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
         int32_t *val_a = (int32_t*)q.val_a.p, *val_b = (int32_t*)q.val_b.p;
         tp_launch_vertices(s, nv, (const int32_t*)q.used.p, vparent, (int32_t*)q.loop_cnt.p, cnt);
         tp_launch_emit(s, faces, nf, flag, off, key_a, val_a);
-        sort_pairs_u64(s, r->tree.temp.p, r->tree.temp.bytes, key_a, key_b, val_a, val_b, (int)n_half, 32 + tp_key_bits(nv));
+        sort_pairs_u64(s, r->tree.temp.p, r->tree.temp.bytes, key_a, key_b, val_a, val_b, (int)n_half, 32 + rc_index_bits(nv));
         tp_launch_classify(s, key_b, val_b, n_half, faces, parent, vparent, cnt);
     }
     if (nf > 0) {
@@ -129,26 +111,22 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
             tp_launch_largest(s, root, num, (const int32_t*)q.nfaces.p, nf, cnt);
         }
     }
-    HIPCHK(c, hipEventRecord(q.ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(h, cnt, TP_COUNTERS * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&q.ms[0], q.ev[0], q.ev[1]);
+    if ((rc = rc_pass_end(r, q, 0, 1, 0, 0, TP_COUNTERS))) return rc;
     if (h[TP_ERROR]) {
         c->err = "topology_analyse: a union did not finish within its step bound (a defect of the library)";
         return IMMESH_E_INTERNAL;
     }
-    int64_t* st = q.st;
-    st[ST_FACES] = nf; st[ST_COUNTING] = n_counting; st[ST_DEGENERATE] = nf - n_counting;
-    st[ST_VERTICES] = (int64_t)h[TP_N_VERTICES]; st[ST_EDGES] = (int64_t)h[TP_N_EDGES];
-    st[ST_BOUNDARY] = (int64_t)h[TP_N_BOUNDARY]; st[ST_INTERIOR] = (int64_t)h[TP_N_INTERIOR]; st[ST_NONMANIFOLD] = (int64_t)h[TP_N_NONMANIFOLD];
-    st[ST_INCONSISTENT] = (int64_t)h[TP_N_INCONSISTENT];
-    st[ST_COMPONENTS] = (int64_t)h[TP_N_COMPONENTS]; st[ST_LARGEST] = (int64_t)h[TP_LARGEST_COMPONENT];
-    st[ST_LOOPS] = (int64_t)h[TP_N_LOOPS]; st[ST_LARGEST_LOOP] = (int64_t)h[TP_LARGEST_LOOP];
-    st[ST_EULER] = st[ST_VERTICES] - st[ST_EDGES] + n_counting;
+    immesh_topology_stats& st = q.st;
+    st.n_faces = nf; st.n_counting = n_counting; st.n_degenerate = nf - n_counting;
+    st.n_vertices_used = (int64_t)h[TP_N_VERTICES]; st.n_edges = (int64_t)h[TP_N_EDGES];
+    st.n_boundary = (int64_t)h[TP_N_BOUNDARY]; st.n_interior = (int64_t)h[TP_N_INTERIOR]; st.n_nonmanifold = (int64_t)h[TP_N_NONMANIFOLD];
+    st.n_inconsistent = (int64_t)h[TP_N_INCONSISTENT];
+    st.n_components = (int64_t)h[TP_N_COMPONENTS]; st.largest_component_faces = (int64_t)h[TP_LARGEST_COMPONENT];
+    st.n_boundary_loops = (int64_t)h[TP_N_LOOPS]; st.largest_loop_edges = (int64_t)h[TP_LARGEST_LOOP];
+    st.euler = st.n_vertices_used - st.n_edges + n_counting;
     q.n_counting = n_counting; q.n_half = n_half;
     q.have = true;
-    if (stats) std::memcpy(stats, st, sizeof(*stats));
+    if (stats) *stats = st;
     return 0;
 }
 
@@ -156,59 +134,44 @@ int immesh_topology_faces(immesh_raycaster* r, int32_t* comp_out) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = tp_analysed(r, "topology_faces"))) return rc;
+    if ((rc = rc_analysed(r, "topology_faces"))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if (comp_out && r->n_faces > 0) HIPCHK(c, hipMemcpy(comp_out, r->tp.comp.p, (size_t)r->n_faces * 4, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_fetch(c, comp_out, r->tp.comp.p, (size_t)r->n_faces * 4);
 }
 
 int immesh_topology_components(immesh_raycaster* r, int32_t* first_face, int32_t* n_faces, int32_t* n_boundary, float* box, int64_t cap, int64_t* n_out) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = tp_analysed(r, "topology_components"))) return rc;
-    if (cap < 0) { c->err = "topology_components: cap is negative"; return IMMESH_E_INVAL; }
+    if ((rc = rc_analysed(r, "topology_components"))) return rc;
     const RcTopology& q = r->tp;
-    const int64_t n = q.st[ST_COMPONENTS];
-    if (n_out) *n_out = n;
-    if ((!first_face && !n_faces && !n_boundary && !box) || n == 0) return 0;
-    if (cap < n) {
-        c->err = "topology_components: cap " + std::to_string(cap) + " < " + std::to_string(n) + " components";
-        return IMMESH_E_CAPACITY;
-    }
+    const int64_t n = q.st.n_components;
+    const bool wanted = first_face || n_faces || n_boundary || box;
+    if ((rc = rc_cap(c, "topology_components", cap, n, n_out, wanted, "components"))) return rc;
+    if (!wanted || n == 0) return 0;
     (void)hipSetDevice(c->cfg.device);
-    if (first_face) HIPCHK(c, hipMemcpy(first_face, q.first.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (n_faces) HIPCHK(c, hipMemcpy(n_faces, q.nfaces.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (n_boundary) HIPCHK(c, hipMemcpy(n_boundary, q.nbound.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (box) {
-        std::vector<uint32_t> keys((size_t)n * 6);
-        HIPCHK(c, hipMemcpy(keys.data(), q.box.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < 6 * n; i++) box[i] = tp_unkey_host(keys[(size_t)i], i % 6 < 3);
-    }
-    return 0;
+    if ((rc = rc_fetch(c, first_face, q.first.p, (size_t)n * 4))) return rc;
+    if ((rc = rc_fetch(c, n_faces, q.nfaces.p, (size_t)n * 4))) return rc;
+    if ((rc = rc_fetch(c, n_boundary, q.nbound.p, (size_t)n * 4))) return rc;
+    return box ? tp_fetch_boxes(c, box, q.box, n) : 0;
 }
 
 int immesh_topology_edges(immesh_raycaster* r, int32_t kind, int32_t* uv, int32_t* uses, int64_t cap, int64_t* n_out) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = tp_analysed(r, "topology_edges"))) return rc;
+    if ((rc = rc_analysed(r, "topology_edges"))) return rc;
     if (kind != IMMESH_EDGE_BOUNDARY && kind != IMMESH_EDGE_NONMANIFOLD && kind != IMMESH_EDGE_INCONSISTENT) {
         c->err = "topology_edges: unknown kind " + std::to_string(kind);
         return IMMESH_E_INVAL;
     }
-    if (cap < 0) { c->err = "topology_edges: cap is negative"; return IMMESH_E_INVAL; }
     RcTopology& q = r->tp;
-    const int64_t n = q.st[kind == IMMESH_EDGE_BOUNDARY ? ST_BOUNDARY : kind == IMMESH_EDGE_NONMANIFOLD ? ST_NONMANIFOLD : ST_INCONSISTENT];
-    if (n_out) *n_out = n;
+    const int64_t n = kind == IMMESH_EDGE_BOUNDARY ? q.st.n_boundary : kind == IMMESH_EDGE_NONMANIFOLD ? q.st.n_nonmanifold : q.st.n_inconsistent;
+    if ((rc = rc_cap(c, "topology_edges", cap, n, n_out, uv || uses, "edges"))) return rc;
     if ((!uv && !uses) || n == 0) return 0;
-    if (cap < n) {
-        c->err = "topology_edges: cap " + std::to_string(cap) + " < " + std::to_string(n) + " edges";
-        return IMMESH_E_CAPACITY;
-    }
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
-    const int64_t n_half = q.n_half, n_edges = q.st[ST_EDGES];
+    const int64_t n_half = q.n_half, n_edges = q.st.n_edges;
     if ((rc = tp_temp(r, n_half, 1))) return rc;
     if ((rc = tp_grow(r, q.head, (size_t)n_half * 4))) return rc;
     if ((rc = tp_grow(r, q.eid, (size_t)n_half * 4))) return rc;
@@ -227,9 +190,8 @@ int immesh_topology_edges(immesh_raycaster* r, int32_t kind, int32_t* uv, int32_
     tp_launch_edges(s, start, n_edges, key, pick, poff, (int32_t*)q.uv.p, (int32_t*)q.uses.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
-    if (uv) HIPCHK(c, hipMemcpy(uv, q.uv.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (uses) HIPCHK(c, hipMemcpy(uses, q.uses.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_fetch(c, uv, q.uv.p, (size_t)n * 8))) return rc;
+    return rc_fetch(c, uses, q.uses.p, (size_t)n * 4);
 }
 
 int immesh_topology_select(immesh_raycaster* r, int64_t min_faces, double min_diagonal, int64_t keep_largest, int8_t* keep_out, int32_t* faces_out,
@@ -237,15 +199,15 @@ int immesh_topology_select(immesh_raycaster* r, int64_t min_faces, double min_di
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
     int rc;
-    if ((rc = tp_analysed(r, "topology_select"))) return rc;
+    if ((rc = rc_analysed(r, "topology_select"))) return rc;
     if (min_faces < 0) { c->err = "topology_select: min_faces is negative"; return IMMESH_E_INVAL; }
     if (keep_largest < 0) { c->err = "topology_select: keep_largest is negative"; return IMMESH_E_INVAL; }
     if (!(min_diagonal >= 0.0) || !std::isfinite(min_diagonal)) { c->err = "topology_select: need 0 <= min_diagonal, finite"; return IMMESH_E_INVAL; }
-    if (cap < 0) { c->err = "topology_select: cap is negative"; return IMMESH_E_INVAL; }
+    if ((rc = rc_cap_negative(c, "topology_select", cap))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     RcTopology& q = r->tp;
-    const int64_t nf = r->n_faces, n_comp = q.st[ST_COMPONENTS];
+    const int64_t nf = r->n_faces, n_comp = q.st.n_components;
     int64_t kept = 0;
     if (nf > 0) {
         if ((rc = tp_temp(r, nf, n_comp))) return rc;
@@ -273,22 +235,12 @@ int immesh_topology_select(immesh_raycaster* r, int64_t min_faces, double min_di
         exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, (const int32_t*)q.keep32.p, (int32_t*)q.koff.p, (int)nf);
         tp_launch_compact(s, (const int32_t*)r->faces.p, (const int32_t*)q.keep32.p, (const int32_t*)q.koff.p, nf, (int32_t*)q.out.p,
                           (unsigned long long*)q.cnt.p);
-        HIPCHK(c, hipEventRecord(q.ev[3], s));
-        HIPCHK(c, hipMemcpyAsync(&q.h_cnt[TP_N_KEPT], (unsigned long long*)q.cnt.p + TP_N_KEPT, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(s));
-        (void)hipEventElapsedTime(&q.ms[1], q.ev[2], q.ev[3]);
+        if ((rc = rc_pass_end(r, q, 2, 3, 1, TP_N_KEPT, 1))) return rc;
         kept = (int64_t)q.h_cnt[TP_N_KEPT];
-        if (keep_out) HIPCHK(c, hipMemcpy(keep_out, q.keep8.p, (size_t)nf, hipMemcpyDeviceToHost));
+        if ((rc = rc_fetch(c, keep_out, q.keep8.p, (size_t)nf))) return rc;
     }
-    if (n_kept) *n_kept = kept;
-    if (!faces_out || kept == 0) return 0;
-    if (cap < kept) {
-        c->err = "topology_select: cap " + std::to_string(cap) + " < " + std::to_string(kept) + " kept faces";
-        return IMMESH_E_CAPACITY;
-    }
-    HIPCHK(c, hipMemcpy(faces_out, q.out.p, (size_t)kept * 12, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = rc_cap(c, "topology_select", cap, kept, n_kept, faces_out != nullptr, "kept faces"))) return rc;
+    return rc_fetch(c, faces_out, q.out.p, (size_t)kept * 12);
 }
 
 int immesh_topology_last_timing(immesh_raycaster* r, float ms[2]) {
