@@ -226,6 +226,15 @@ VERTEX_UNUSED, VERTEX_NOT_FINITE, VERTEX_BORDER, VERTEX_INTERIOR = 0, 1, 2, 3
 SMOOTH_BORDER_FIXED, SMOOTH_BORDER_ALONG, SMOOTH_BORDER_FREE = 0, 1, 2
 
 
+class IntersectStats(C.Structure):
+    """immesh_intersect_stats (include/immesh_intersect.h): the counts of the last self-intersection pass over the caster's snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_faces", "n_in_tree", "n_taking_part", "n_candidates")] + [("n_share", C.c_int64 * 4)] + \
+               [(n, C.c_int64) for n in ("n_pairs", "n_pairs_share0", "n_pairs_share1", "n_faces_hit", "max_partners")]
+
+
+assert C.sizeof(IntersectStats) == 104
+
+
 class Image(C.Structure):
     """immesh_image (include/immesh_colour.h): one camera frame, its intrinsics, pose, exposure and gates"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("row_stride_bytes", C.c_int64),
@@ -1178,6 +1187,47 @@ class HotPath:
         n = C.c_int64(0)
         self._check(f(self.raycaster(), _ptr(out) if fetch else None, C.byref(n)), "vertex_normals")
         return out, n.value
+
+    # -- self-intersections of the caster's snapshot (include/immesh_intersect.h) -----------------------------------------------------------------------
+    def self_intersect(self, max_candidates=1 << 24):
+        """immesh_self_intersect on the caster's snapshot: the candidate pairs (faces that take part, float boxes overlapping), their segment tests,
+        the intersecting pairs and per face the number it is in -> IntersectStats; the result stays on the device for the calls below.  More than
+        max_candidates candidates raise (rc=-4)"""
+        f = self.lib.immesh_self_intersect; f.argtypes = [C.c_void_p, C.c_int64, C.POINTER(IntersectStats)]; f.restype = C.c_int
+        st = IntersectStats()
+        self._check(f(self.raycaster(), max_candidates, C.byref(st)), "self_intersect")
+        return st
+
+    def self_intersect_pairs(self):
+        """the intersecting pairs in ascending (i, j) -> (pairs (n_pairs, 2) int32, mask (n_pairs,) uint8)"""
+        f = self.lib.immesh_self_intersect_pairs; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, 0, C.byref(n)), "self_intersect_pairs")
+        pairs, mask = np.empty((n.value, 2), np.int32), np.empty(n.value, np.uint8)
+        self._check(f(self.raycaster(), _ptr(pairs), _ptr(mask), n.value, C.byref(n)), "self_intersect_pairs")
+        return pairs, mask
+
+    def self_intersect_faces(self):
+        """-> dict: n_partners (n_faces,) int32, face_map (n_faces,) int32 (the index after an apply, -1: the face goes)"""
+        f = self.lib.immesh_self_intersect_faces; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster(), None, None), "self_intersect_faces")
+        nf = self._raycast_sizes()[1]
+        out = {"n_partners": np.empty(nf, np.int32), "face_map": np.empty(nf, np.int32)}
+        self._check(f(self.raycaster(), _ptr(out["n_partners"]), _ptr(out["face_map"])), "self_intersect_faces")
+        return out
+
+    def self_intersect_apply(self):
+        """immesh_self_intersect_apply: the faces without a partner become the caster's, on the device, and its hierarchy is built again; everything a
+        build discards is discarded"""
+        f = self.lib.immesh_self_intersect_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "self_intersect_apply")
+
+    def self_intersect_timing(self):
+        """device milliseconds of the last (candidates, tests and sort, apply)"""
+        f = self.lib.immesh_self_intersect_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.raycaster(), ms), "self_intersect_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # -- shaded and coloured images of the mesh (include/immesh_shade.h) -------------------------------------------------------------------------
     def default_shade(self, **over):

@@ -7,6 +7,7 @@
 #include "../../../include/immesh_topology.h"    // the stats the passes' records hold
 #include "../../../include/immesh_simplify.h"
 #include "../../../include/immesh_smooth.h"
+#include "../../../include/immesh_intersect.h"
 
 constexpr int RC_BLOCK = 256;
 // The sort key of a face is (Morton code of its box centre, position among the faces that enter the tree): RC_CODE_BITS + RC_INDEX_BITS bits, all
@@ -159,7 +160,7 @@ struct RcSample {
     }
 };
 
-// What the five passes over the snapshot share (analysis, orientation, holes, simplification, smoothing): the events of their spans, the device
+// What the six passes over the snapshot share (analysis, orientation, holes, simplification, smoothing, self-intersections): the events of their spans, the device
 // counters and their pinned copy, all created by rc_pass_ready at the pass' first call and never before; `have`: a result of the current snapshot (of
 // the current analysis, for the orientation and the holes) exists.  rc_snapshot_changed / rc_analysis_changed below clear it.
 struct RcPass {
@@ -233,6 +234,16 @@ struct RcSmooth : RcPass {                                     // spans: one-rin
     immesh_smooth_stats st = {};
 };
 
+// the self-intersections of the snapshot (include/immesh_intersect.h; intersect/intersect_host.cpp): allocated at the first immesh_self_intersect,
+// never before.  It needs no analysis: it reads the caster's vertex and face buffers and its hierarchy.
+struct RcIntersect : RcPass {                                  // spans: candidates, tests, apply
+    RcBuf take, cnt32, off, npart, keep, koff, fmap;           // per face (take: int8)
+    RcBuf key, cmask, flag, hoff;                              // per candidate: (i << 32) | j, the pair mask (uint8), mask != 0 and its scan
+    RcBuf hkey_a, hkey_b, hval_a, hval_b, pairs, pmask;        // per hit: the sort's buffers (_b sorted), then i, j as int32 and the mask as uint8
+    RcBuf faces_out;                                           // the apply's kept faces: they change places with the caster's face buffer
+    immesh_intersect_stats st = {};
+};
+
 // the caster (include/immesh_raycast.h, include/immesh_closest.h): raycast_host.cpp owns it, closest_host.cpp adds its queries
 struct immesh_raycaster {
     immesh_ctx* ctx = nullptr;
@@ -258,6 +269,7 @@ struct immesh_raycaster {
     RcHoles hl;
     RcSimplify sp;
     RcSmooth so;
+    RcIntersect ix;
 };
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream); it discards what belongs to the snapshot before
 int rc_build(immesh_raycaster* r, int64_t n_vtx, int64_t n_faces);

@@ -187,6 +187,7 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
 //   the orientation (ot), the holes pass (hl)    | discarded (they read the analysis) | discarded
 //   the simplification's result (sp)             | discarded             | stays
 //   the smoothing pass' result (so)              | discarded             | stays
+//   the intersection pass' result (ix)           | discarded             | stays
 //   the closest-point results of the last query  | stay                  | stay
 //
 // The closest-point results stay readable on purpose: they are answers about the points of a query, not a view of the snapshot.  immesh_raycast
@@ -204,6 +205,7 @@ void rc_snapshot_changed(immesh_raycaster* r) {
     rc_analysis_changed(r);
     r->sp.have = false;
     r->so.have = false;
+    r->ix.have = false;
 }
 
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)

@@ -5,7 +5,8 @@
   chamfer       the sum of the two mean distances
   precision, recall, F-score at tau: the share of samples / of ground-truth points nearer than tau, from the two histograms with bin_width = tau
                 (bin 0 is dist < tau), over the points that are finite; 2 P R / (P + R)
-Six options look at the mesh itself first (include/immesh_simplify.h, include/immesh_topology.h, include/immesh_smooth.h), all off by default:
+Eight options look at the mesh itself first (include/immesh_simplify.h, include/immesh_topology.h, include/immesh_smooth.h,
+include/immesh_intersect.h), all off by default:
   --weld | --simplify CELL [--simplify-mode first|mean] [--keep-duplicate-faces]
                             first of all, before the fragment filter: weld the vertices of equal coordinates (--weld: a soup that repeats its vertices
                             becomes a mesh whose faces share indices) or cluster them on a grid of CELL (--simplify: the decimation), drop the faces
@@ -30,6 +31,14 @@ Six options look at the mesh itself first (include/immesh_simplify.h, include/im
                             Taubin smoothing over the one-ring (immesh_smooth; L = 0.5 and M = -0.53 by default, M = L is plain Laplacian smoothing;
                             the border vertices stay, slide along the border or move freely), and the caster gets the moved vertices on the device
                             (immesh_smooth_apply).  The output gains a `smooth` block: the arguments and the pass' counts
+  --remove-self-intersections [--max-candidates N]
+                            right after --weld / --simplify and before the fragment filter: find the pairs of faces that pass through each other
+                            (immesh_self_intersect) and take every face of such a pair out on the device (immesh_self_intersect_apply); the fragment
+                            filter, the orientation and --fill-holes then see the holes it left.  The output gains an `intersections_removed` block:
+                            the pass' counts and the faces that went.  Weld first: the neighbours of an unwelded soup touch and count
+  --self-intersections [--max-candidates N]
+                            the self-intersection counts of the mesh that is evaluated, after every other clean-up option, in an `intersections`
+                            block.  N bounds the candidate pairs of either option (2^24 by default): a mesh with more is refused
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
@@ -38,6 +47,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--fill-holes MAX_EDGES [--fill-max-diagonal D]]
                               [--weld | --simplify CELL [--simplify-mode first|mean]] [--keep-duplicate-faces]
                               [--smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]]
+                              [--remove-self-intersections] [--self-intersections] [--max-candidates N]
 """
 import argparse
 import json
@@ -155,6 +165,24 @@ def smooth(h, n_steps, lam=0.5, mu=-0.53, border="fixed"):
     return {"lambda": lam, "mu": mu, "border": border, **{n: getattr(st, n) for n, _ in capi.SmoothStats._fields_}}
 
 
+def _intersect_stats(st):
+    return {n: (list(st.n_share) if n == "n_share" else getattr(st, n)) for n, _ in capi.IntersectStats._fields_}
+
+
+def self_intersections(h, max_candidates=1 << 24):
+    """the self-intersection counts of the built caster's mesh -> dict"""
+    return {"max_candidates": max_candidates, **_intersect_stats(h.self_intersect(max_candidates))}
+
+
+def remove_self_intersections(h, faces, max_candidates=1 << 24):
+    """h: a HotPath with a built caster over `faces` -> the faces of every intersecting pair taken out on the device (self_intersect, apply); returns
+    (the caster's sizes, the kept faces as the later steps need them on the host, the counts and what went)"""
+    st = h.self_intersect(max_candidates)
+    kept = faces[h.self_intersect_faces()["face_map"] >= 0]
+    h.self_intersect_apply()
+    return h._raycast_sizes(), kept, {"max_candidates": max_candidates, **_intersect_stats(st), "faces_before": len(faces), "faces_removed": len(faces) - len(kept)}
+
+
 def topology(h):
     """the counts of the built caster's mesh -> dict"""
     st = h.topology_analyse()
@@ -184,7 +212,13 @@ def main():
     ap.add_argument("--smooth-lambda", type=float, default=None, metavar="L", help="with --smooth: the factor of the even steps (0.5)")
     ap.add_argument("--smooth-mu", type=float, default=None, metavar="M", help="with --smooth: the factor of the odd steps (-0.53; M = L: Laplacian smoothing)")
     ap.add_argument("--smooth-border", choices=sorted(SMOOTH_BORDERS), default=None, help="with --smooth: what a border vertex does (fixed)")
+    ap.add_argument("--remove-self-intersections", action="store_true", help="take the faces that pass through each other out, right after --weld / --simplify")
+    ap.add_argument("--self-intersections", action="store_true", help="add the evaluated mesh's self-intersection counts to the output")
+    ap.add_argument("--max-candidates", type=int, default=None, metavar="N", help="with either of the two: refuse a mesh with more candidate pairs (2^24)")
     args = ap.parse_args()
+    if args.max_candidates is not None and not (args.remove_self_intersections or args.self_intersections):
+        ap.error("--max-candidates N goes with --remove-self-intersections or --self-intersections")
+    max_candidates = (1 << 24) if args.max_candidates is None else args.max_candidates
     if args.smooth is None and (args.smooth_lambda is not None or args.smooth_mu is not None or args.smooth_border is not None):
         ap.error("--smooth-lambda, --smooth-mu and --smooth-border go with --smooth N_STEPS")
     if args.smooth is not None and args.smooth < 0:
@@ -205,6 +239,8 @@ def main():
         extra = {}
         if args.weld or args.simplify is not None:
             sizes, vtx, faces, extra["simplify"] = simplify(h, 0.0 if args.weld else args.simplify, args.simplify_mode, not args.keep_duplicate_faces)
+        if args.remove_self_intersections:
+            sizes, faces, extra["intersections_removed"] = remove_self_intersections(h, faces, max_candidates)
         if args.min_component_faces > 0:
             sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
         if args.orient:
@@ -216,6 +252,8 @@ def main():
                                      args.smooth_border or "fixed")
         if args.topology:
             extra["topology"] = topology(h)
+        if args.self_intersections:
+            extra["intersections"] = self_intersections(h, max_candidates)
         out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
                    **extra)
     finally:
