@@ -10,36 +10,22 @@
 // Double arithmetic is written in the contract's order; the library builds with -ffp-contract=off, so nothing is fused.
 #include "intersect.hpp"
 #include "../raycast/raycast_dev.hpp"
+#include "../raycast/pass_dev.hpp"   // the folds of the counters (64 bits: a lane of the walk counts up to n_faces candidates), the rule "a face counts"
 
 namespace {
 
-// sums v over the workgroup and adds the total to *dst (one atomic per workgroup; every lane of the workgroup calls it)
-__device__ __forceinline__ void ix_block_add(unsigned long long v, unsigned long long* dst) {
-    __shared__ unsigned long long s_sum[RC_BLOCK];
-    __syncthreads();                                  // a second call reuses the array
-    s_sum[threadIdx.x] = v;
-    for (int stride = RC_BLOCK / 2; stride >= 1; stride >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < stride) s_sum[threadIdx.x] += s_sum[threadIdx.x + stride];
-    }
-    if (threadIdx.x == 0 && s_sum[0]) atomicAdd(dst, s_sum[0]);
-}
-
 __global__ void __launch_bounds__(RC_BLOCK) ix_take_kernel(const float* __restrict__ vtx, int64_t n_vtx, const int32_t* __restrict__ faces, int64_t n_faces,
                                                            int8_t* __restrict__ take, unsigned long long* cnt) {
+    __shared__ unsigned long long lds[RC_BLOCK / 64];
     const int64_t f = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     bool ok = false;
     if (f < n_faces) {
-        const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-        ok = a != b && b != c && a != c;
-        const int32_t id[3] = {a, b, c};
-        for (int k = 0; k < 3; k++) {
-            if (id[k] < 0 || (int64_t)id[k] >= n_vtx) { ok = false; break; }   // (the hierarchy's mark: such a face is not in the tree)
-            for (int j = 0; j < 3; j++) ok = ok && isfinite(vtx[3 * (int64_t)id[k] + j]);
-        }
+        const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+        // (an index out of range or a vertex that is not finite is the hierarchy's mark: such a face is not in the tree)
+        ok = pd_counts(a, b, c, n_vtx) && pd_finite3(vtx, a) && pd_finite3(vtx, b) && pd_finite3(vtx, c);
         take[f] = ok ? 1 : 0;
     }
-    ix_block_add(ok ? 1ull : 0ull, cnt + IX_N_TAKING);
+    pd_block_add<unsigned long long>(ok ? 1ull : 0ull, cnt + IX_N_TAKING, lds);
 }
 
 // closed overlap of two float boxes on all three axes
@@ -53,6 +39,7 @@ __global__ void __launch_bounds__(RC_BLOCK) ix_walk_kernel(const float* __restri
                                                            const int8_t* __restrict__ take, const RcNode* __restrict__ nodes, int64_t n_in,
                                                            int32_t* __restrict__ cnt32, const int32_t* __restrict__ off,
                                                            unsigned long long* __restrict__ keys, unsigned long long* cnt) {
+    __shared__ unsigned long long lds[RC_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     unsigned long long k = 0;
     if (i < n_faces && n_in > 0 && take[i]) {
@@ -88,7 +75,7 @@ __global__ void __launch_bounds__(RC_BLOCK) ix_walk_kernel(const float* __restri
     }
     if (!EMIT) {
         if (i < n_faces) cnt32[i] = k > 0x7FFFFFFFull ? 0x7FFFFFFF : (int32_t)k;   // (a total with such a face is refused before the offsets are read)
-        ix_block_add(k, cnt + IX_N_CANDIDATES);
+        pd_block_add<unsigned long long>(k, cnt + IX_N_CANDIDATES, lds);
     }
 }
 
@@ -193,18 +180,16 @@ __global__ void __launch_bounds__(RC_BLOCK) ix_pairs_kernel(const unsigned long 
 
 __global__ void __launch_bounds__(RC_BLOCK) ix_keep_kernel(const int32_t* __restrict__ npart, int64_t n_faces, int32_t* __restrict__ keep,
                                                            unsigned long long* cnt) {
-    __shared__ unsigned int s_max;
-    if (threadIdx.x == 0) s_max = 0;
+    __shared__ unsigned long long lds[RC_BLOCK / 64];
+    __shared__ uint32_t lds_max[RC_BLOCK / 64];
     const int64_t f = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     int32_t p = 0;
     if (f < n_faces) {
         p = npart[f];
         keep[f] = p == 0 ? 1 : 0;
     }
-    ix_block_add(p > 0 ? 1ull : 0ull, cnt + IX_N_FACES_HIT);     // (its first barrier orders s_max's reset)
-    if (p > 0) atomicMax(&s_max, (unsigned int)p);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_max) atomicMax(cnt + IX_MAX_PARTNERS, (unsigned long long)s_max);
+    pd_block_add<unsigned long long>(p > 0 ? 1ull : 0ull, cnt + IX_N_FACES_HIT, lds);
+    pd_block_max(p > 0 ? (uint32_t)p : 0u, cnt + IX_MAX_PARTNERS, lds_max);
 }
 
 __global__ void __launch_bounds__(RC_BLOCK) ix_map_kernel(const int32_t* __restrict__ faces, int64_t n_faces, const int32_t* __restrict__ keep,

@@ -8,6 +8,7 @@
 // Double arithmetic is written in the contract's order; the library builds with -ffp-contract=off, so nothing is fused.
 #include "raycast.hpp"
 #include "raycast_dev.hpp"
+#include "pass_dev.hpp"   // the sampler's fold of its total
 
 namespace {
 
@@ -78,7 +79,7 @@ __device__ __forceinline__ bool ms_face(const float* __restrict__ vtx, int64_t n
 
 __global__ void __launch_bounds__(RC_BLOCK) ms_count_kernel(const float* __restrict__ vtx, int64_t n_vtx, const int32_t* __restrict__ faces, int64_t n_faces,
                                                             double density, unsigned long long seed, int32_t* __restrict__ cnt, unsigned long long* total) {
-    __shared__ unsigned long long s_sum[RC_BLOCK];
+    __shared__ unsigned long long lds[RC_BLOCK / 64];
     const int64_t f = (int64_t)blockIdx.x * RC_BLOCK + threadIdx.x;
     unsigned long long k = 0;
     if (f < n_faces) {
@@ -96,12 +97,7 @@ __global__ void __launch_bounds__(RC_BLOCK) ms_count_kernel(const float* __restr
         }
         cnt[f] = k > 0x7FFFFFFFull ? 0x7FFFFFFF : (int32_t)k;   // (a total with such a face is refused before the offsets are read)
     }
-    s_sum[threadIdx.x] = k;
-    for (int stride = RC_BLOCK / 2; stride >= 1; stride >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < stride) s_sum[threadIdx.x] += s_sum[threadIdx.x + stride];
-    }
-    if (threadIdx.x == 0 && s_sum[0]) atomicAdd(total, s_sum[0]);
+    pd_block_add<unsigned long long>(k, total, lds);            // 64 bits: a face counts up to 2^31 samples
 }
 
 __device__ __forceinline__ void ms_sample(const double* A, const double* ab, const double* ac, unsigned long long hf, int64_t j, float* out) {

@@ -8,15 +8,9 @@
 // Double arithmetic is written in the contract's order; the library builds with -ffp-contract=off, so nothing is fused.
 #include "raycast.hpp"
 #include "raycast_dev.hpp"
+#include "pass_dev.hpp"   // the order-preserving float keys
 
 namespace {
-
-// floats <-> unsigned keys of the same order
-__device__ __forceinline__ uint32_t rc_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rc_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // ---- build ------------------------------------------------------------------------------------------------------------------------------
 // SOUP: the items are the faces of src; else the points of the cloud src.xyz
@@ -57,7 +51,7 @@ __global__ void __launch_bounds__(RC_BLOCK) rc_compact_kernel(RcLeaves src, int6
             }
             box[6 * i + j] = lo;
             box[6 * i + 3 + j] = hi;
-            const uint32_t k = rc_key(0.5f * lo + 0.5f * hi);   // the centre, as rc_codes_kernel computes it from the box; halves first, so it cannot overflow
+            const uint32_t k = pd_key(0.5f * lo + 0.5f * hi);   // the centre, as rc_codes_kernel computes it from the box; halves first, so it cannot overflow
             atomicMin(&s_b[j], k);
             atomicMax(&s_b[3 + j], k);
         }
@@ -85,7 +79,7 @@ __global__ void __launch_bounds__(RC_BLOCK) rc_codes_kernel(const float* __restr
     if (i >= n_in) return;
     unsigned long long c = 0;
     for (int j = 0; j < 3; j++) {
-        const double lo = (double)rc_unkey(bounds[j]), hi = (double)rc_unkey(bounds[3 + j]);
+        const double lo = (double)pd_unkey(bounds[j]), hi = (double)pd_unkey(bounds[3 + j]);
         const double ctr = (double)(0.5f * box[6 * i + j] + 0.5f * box[6 * i + 3 + j]);
         const double ext = hi - lo;
         double q = ext > 0.0 ? ((ctr - lo) / ext) * 2097152.0 : 0.0;       // 2^21 cells per axis

@@ -9,7 +9,8 @@
 //   mean       one lane per cluster sums its run in the sorted order, which is ascending vertex index: the order IS the contract, so this walk is the
 //              one place a lane follows a run, bounded by the run's length and by n_vtx
 //   faces / duplicates / compact   the mapped triples; the kept candidates sorted by their sorted triple, the non-heads of a run are the duplicates
-//   counters   integers, folded per workgroup before one atomic each
+//   counters   integers, folded per workgroup before one atomic each (pass_dev.hpp's folds; the four launches that count go over their items in a
+//              grid-stride loop, pd_grid_capped)
 // Integers, float bits and one sequential double sum (compiled with -ffp-contract=off): the results do not depend on the order of anything.  Every
 // scatter index is checked against its room before the store.
 #include "simplify.hpp"
@@ -18,41 +19,10 @@
 
 namespace {
 
-// The four launches that count go over their items in a grid-stride loop with at most SP_MAX_BLOCKS workgroups, keep their counts in registers and
-// send one atomic per workgroup and counter at the end: one atomic per wavefront on one word (46 000 of them at 2 952 000 vertices) cost 12 ns
-// each, one after the other, which was a third of the weld's pass.
-constexpr int SP_MAX_BLOCKS = 1024;
-inline unsigned sp_grid(int64_t n) { return (unsigned)(tp_grid(n) < (unsigned)SP_MAX_BLOCKS ? tp_grid(n) : (unsigned)SP_MAX_BLOCKS); }
-
-__device__ __forceinline__ uint32_t sp_wave_sum(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// word += the workgroup's sum of v / word = max(word, the workgroup's largest v): every lane of the workgroup calls these, once, after its loop
-// (a lane's count stays below 2^31 / 2^18, a workgroup's below 2^31)
-__device__ __forceinline__ void sp_block_add(uint32_t v, unsigned long long* word, uint32_t* lds) {
-    v = sp_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < TP_BLOCK / 64; w++) t += lds[w];
-        if (t) atomicAdd(word, (unsigned long long)t);
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void sp_block_max(uint32_t v, unsigned long long* word, uint32_t* lds) {
-    v = tp_wave_max(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < TP_BLOCK / 64; w++) t = lds[w] > t ? lds[w] : t;
-        if (t) atomicMax(word, (unsigned long long)t);
-    }
-    __syncthreads();
-}
-
+// sp_mark_kernel and sp_faces_kernel write the rule "a face counts" out, as they did before pass_dev.hpp, and do not call its pd_counts: through
+// the function (here or as a private helper of this file) both kernels compile to other instructions, one apart and with two to three VGPRs more,
+// and the simplify span then measured 0.005 ms above the parent's median in all seven cases of tools/simplify_bench.py over seven alternating runs,
+// above the parent's range in one (0.5698 ms over 0.5604 - 0.5685).  Written out, both kernels are the parent's instruction for instruction.
 __global__ void __launch_bounds__(TP_BLOCK) sp_mark_kernel(const int32_t* __restrict__ faces, int64_t n_faces, int64_t n_vtx, int32_t* state) {
     const int64_t f = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
     if (f >= n_faces) return;
@@ -76,7 +46,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_keys_kernel(const float* __restri
         uint32_t lo = 0xFFFFFFFFu;
         if (st == SP_NORMAL) {
             const float x[3] = {vtx[3 * v], vtx[3 * v + 1], vtx[3 * v + 2]};
-            if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) st = SP_ALONE_NOT_FINITE;
+            if (!pd_finite3(vtx, v)) st = SP_ALONE_NOT_FINITE;
             else if (cell > 0.0) {
                 unsigned long long key = 0;
                 for (int j = 0; j < 3; j++) {
@@ -87,7 +57,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_keys_kernel(const float* __restri
                 if (st == SP_NORMAL) { hi = key; lo = 0u; }
             } else {
                 uint32_t k[3];
-                for (int j = 0; j < 3; j++) k[j] = tp_key(x[j] == 0.0f ? 0.0f : x[j]);  // -0 onto +0
+                for (int j = 0; j < 3; j++) k[j] = pd_key(x[j] == 0.0f ? 0.0f : x[j]);  // -0 onto +0
                 hi = ((unsigned long long)k[0] << 32) | (unsigned long long)k[1];
                 lo = k[2];
             }
@@ -100,9 +70,9 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_keys_kernel(const float* __restri
         n_not_finite += st == SP_ALONE_NOT_FINITE;
         n_outside += st == SP_ALONE_OUTSIDE;
     }
-    sp_block_add(n_used, cnt + SP_N_USED, lds);
-    sp_block_add(n_not_finite, cnt + SP_N_ALONE_NOT_FINITE, lds);
-    sp_block_add(n_outside, cnt + SP_N_ALONE_OUTSIDE, lds);
+    pd_block_add(n_used, cnt + SP_N_USED, lds);
+    pd_block_add(n_not_finite, cnt + SP_N_ALONE_NOT_FINITE, lds);
+    pd_block_add(n_outside, cnt + SP_N_ALONE_OUTSIDE, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sp_gather64_kernel(const unsigned long long* __restrict__ k64, const int32_t* __restrict__ idx, int64_t n,
@@ -177,8 +147,8 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_clusters_kernel(const float* __re
             }
         }
     }
-    sp_block_add(n_mine, cnt + SP_N_CLUSTERS, lds);
-    sp_block_max(largest, cnt + SP_LARGEST, lds);
+    pd_block_add(n_mine, cnt + SP_N_CLUSTERS, lds);
+    pd_block_max(largest, cnt + SP_LARGEST, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sp_mean_kernel(const float* __restrict__ vtx, const int32_t* __restrict__ sv, int64_t n_vtx,
@@ -223,7 +193,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_faces_kernel(const int32_t* __res
         const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
         unsigned long long hi = SP_KEY_APART;
         uint32_t lo = 0xFFFFFFFFu;
-        if (a < 0 || b < 0 || c < 0 || a >= n_vtx || b >= n_vtx || c >= n_vtx || a == b || b == c || a == c) status = IMMESH_FACE_NOT_COUNTING;
+        if (a < 0 || b < 0 || c < 0 || a >= n_vtx || b >= n_vtx || c >= n_vtx || a == b || b == c || a == c) status = IMMESH_FACE_NOT_COUNTING;   // (written out: above)
         else {
             const int32_t g0 = vmap[a], g1 = vmap[b], g2 = vmap[c];
             if (g0 == g1 || g1 == g2 || g0 == g2 || g0 < 0 || g1 < 0 || g2 < 0) status = IMMESH_FACE_COLLAPSED;   // (a used vertex has a cluster: never < 0)
@@ -241,8 +211,8 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_faces_kernel(const int32_t* __res
         n_not_counting += status == IMMESH_FACE_NOT_COUNTING;
         n_collapsed += status == IMMESH_FACE_COLLAPSED;
     }
-    sp_block_add(n_not_counting, cnt + SP_N_NOT_COUNTING, lds);
-    sp_block_add(n_collapsed, cnt + SP_N_COLLAPSED, lds);
+    pd_block_add(n_not_counting, cnt + SP_N_NOT_COUNTING, lds);
+    pd_block_add(n_collapsed, cnt + SP_N_COLLAPSED, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sp_duplicates_kernel(const int32_t* __restrict__ sf, int64_t n_faces, const unsigned long long* __restrict__ f64,
@@ -260,7 +230,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sp_duplicates_kernel(const int32_t* 
             if (dup) { fstatus[f] = IMMESH_FACE_DUPLICATE; keep[f] = 0; n_dup++; }
         }
     }
-    sp_block_add(n_dup, cnt + SP_N_DUPLICATE, lds);
+    pd_block_add(n_dup, cnt + SP_N_DUPLICATE, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sp_compact_kernel(const int32_t* __restrict__ faces, int64_t n_faces, const int32_t* __restrict__ vmap,
@@ -283,7 +253,7 @@ void sp_launch_mark(hipStream_t s, const int32_t* faces, int64_t n_faces, int64_
 }
 void sp_launch_keys(hipStream_t s, const float* vtx, int64_t n_vtx, double cell, int32_t* state, unsigned long long* k64, uint32_t* k32, int32_t* iota,
                     unsigned long long* cnt) {
-    if (n_vtx > 0) sp_keys_kernel<<<sp_grid(n_vtx), TP_BLOCK, 0, s>>>(vtx, n_vtx, cell, state, k64, k32, iota, cnt);
+    if (n_vtx > 0) sp_keys_kernel<<<pd_grid_capped(n_vtx), TP_BLOCK, 0, s>>>(vtx, n_vtx, cell, state, k64, k32, iota, cnt);
 }
 void sp_launch_gather64(hipStream_t s, const unsigned long long* k64, const int32_t* idx, int64_t n, unsigned long long* out) {
     if (n > 0) sp_gather64_kernel<<<tp_grid(n), TP_BLOCK, 0, s>>>(k64, idx, n, out);
@@ -300,7 +270,7 @@ void sp_launch_labels(hipStream_t s, const int32_t* sv, int64_t n_vtx, const int
 }
 void sp_launch_clusters(hipStream_t s, const float* vtx, const int32_t* sv, int64_t n_vtx, const int32_t* state, const int32_t* head, const int32_t* scan,
                         const int32_t* rend, const int32_t* cnum, int32_t* first, int32_t* nmem, int32_t* cstart, float* vtx_out, unsigned long long* cnt) {
-    if (n_vtx > 0) sp_clusters_kernel<<<sp_grid(n_vtx), TP_BLOCK, 0, s>>>(vtx, sv, n_vtx, state, head, scan, rend, cnum, first, nmem, cstart, vtx_out, cnt);
+    if (n_vtx > 0) sp_clusters_kernel<<<pd_grid_capped(n_vtx), TP_BLOCK, 0, s>>>(vtx, sv, n_vtx, state, head, scan, rend, cnum, first, nmem, cstart, vtx_out, cnt);
 }
 void sp_launch_mean(hipStream_t s, const float* vtx, const int32_t* sv, int64_t n_vtx, const int32_t* nmem, const int32_t* cstart, const unsigned long long* cnt,
                     float* vtx_out) {
@@ -311,11 +281,11 @@ void sp_launch_vmap(hipStream_t s, int64_t n_vtx, const int32_t* state, const in
 }
 void sp_launch_faces(hipStream_t s, const int32_t* faces, int64_t n_faces, int64_t n_vtx, const int32_t* vmap, int8_t* fstatus, int32_t* keep,
                      unsigned long long* f64, uint32_t* f32, int32_t* iota, unsigned long long* cnt) {
-    if (n_faces > 0) sp_faces_kernel<<<sp_grid(n_faces), TP_BLOCK, 0, s>>>(faces, n_faces, n_vtx, vmap, fstatus, keep, f64, f32, iota, cnt);
+    if (n_faces > 0) sp_faces_kernel<<<pd_grid_capped(n_faces), TP_BLOCK, 0, s>>>(faces, n_faces, n_vtx, vmap, fstatus, keep, f64, f32, iota, cnt);
 }
 void sp_launch_duplicates(hipStream_t s, const int32_t* sf, int64_t n_faces, const unsigned long long* f64, const uint32_t* f32, int8_t* fstatus, int32_t* keep,
                           unsigned long long* cnt) {
-    if (n_faces > 0) sp_duplicates_kernel<<<sp_grid(n_faces), TP_BLOCK, 0, s>>>(sf, n_faces, f64, f32, fstatus, keep, cnt);
+    if (n_faces > 0) sp_duplicates_kernel<<<pd_grid_capped(n_faces), TP_BLOCK, 0, s>>>(sf, n_faces, f64, f32, fstatus, keep, cnt);
 }
 void sp_launch_compact(hipStream_t s, const int32_t* faces, int64_t n_faces, const int32_t* vmap, const int32_t* keep, const int32_t* koff, int32_t* faces_out,
                        int32_t* fmap, unsigned long long* cnt) {

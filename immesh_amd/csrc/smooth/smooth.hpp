@@ -19,11 +19,8 @@ enum { SM_FLAG_BORDER = 0, SM_FLAG_MOVING = 1, SM_FLAGS = 2 };
 // ---- the one-ring ----------------------------------------------------------------------------------------------------------------------------------------
 // one lane per face: key[6 f .. 6 f + 5] = its six directed pairs, val[6 f + e] = 6 f + e (the sort's values; nothing reads them)
 void sm_launch_emit(hipStream_t s, const int32_t* faces, int64_t n_faces, int64_t n_vtx, unsigned long long* key, int32_t* val);
-// one lane per sorted position: head[i] = 1 where a run of equal keys begins
-void sm_launch_heads(hipStream_t s, const unsigned long long* key, int64_t n6, int32_t* head);
-// after the scan of head (run p = scan[i] of a head): rstart[p] = the head's position; rstart[the number of runs] = n6, so the length of run p is
-// rstart[p + 1] - rstart[p] = uses of its edge: both directions are emitted per use.  rstart has n6 + 1 entries.
-void sm_launch_runs(hipStream_t s, int64_t n6, const int32_t* head, const int32_t* scan, int32_t* rstart);
+// (the run heads of the sorted keys and, after their scan, rstart are raycast/pass_dev.hpp's run kernels: the length of run p is
+// rstart[p + 1] - rstart[p] = uses of its edge: both directions are emitted per use.  rstart has n6 + 1 entries.)
 // one lane per run whose row is a vertex: neighbours[p], uses[p], and flag[SM_FLAG_BORDER n_vtx + u] = 1 for the row u of an edge with uses != 2
 // (every writer stores the same value; flag zeroed by the caller).  The order is already ascending by u, then v.
 void sm_launch_entries(hipStream_t s, const unsigned long long* key, int64_t n6, int64_t n_vtx, const int32_t* head, const int32_t* scan, const int32_t* rstart,

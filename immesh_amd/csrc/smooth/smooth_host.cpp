@@ -10,6 +10,7 @@
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_smooth.h"
 #include "smooth.hpp"
+#include "../raycast/pass_dev.hpp"   // the run kernels of the one-ring
 
 static_assert(sizeof(immesh_smooth_stats) == 12 * 8 && offsetof(immesh_smooth_stats, n_vertices) == 0 && offsetof(immesh_smooth_stats, n_used) == 8 &&
                   offsetof(immesh_smooth_stats, n_not_finite) == 16 && offsetof(immesh_smooth_stats, n_border) == 24 &&
@@ -98,9 +99,9 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         sm_launch_emit(s, (const int32_t*)r->faces.p, nf, nv, key_a, (int32_t*)o.val_a.p);
         sort_pairs_u64(s, temp, temp_bytes, key_a, key_b, (const int32_t*)o.val_a.p, (int32_t*)o.val_b.p, (int)n6, 32 + rc_index_bits(nv + 1));
         int32_t *head = (int32_t*)key_a, *scan = head + n6;     // the unsorted keys are done with: the heads and their scan lie in them
-        sm_launch_heads(s, key_b, n6, head);
+        pd_launch_run_heads(s, key_b, n6, head);
         exclusive_sum_i32(s, temp, temp_bytes, head, scan, (int)n6);
-        sm_launch_runs(s, n6, head, scan, rstart);
+        pd_launch_run_starts(s, n6, head, scan, rstart, n6 + 1);
         sm_launch_entries(s, key_b, n6, nv, head, scan, rstart, neighbours, uses, flag);
         sm_launch_rows(s, vtx, nv, key_b, n6, head, scan, flag, (long long*)o.row_start.p, vclass, cnt);
         sm_launch_lists(s, key_b, n6, nv, head, scan, rstart, neighbours, uses, vclass, border, (int32_t*)o.sn.p, flag);

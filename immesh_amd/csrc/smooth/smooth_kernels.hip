@@ -2,7 +2,8 @@
 // kernels implement).
 //   emit       one lane per face: its six directed pairs as keys (u << 32) | v; a face that does not count emits the key above every real one.  One
 //              64-bit pair sort follows: the pairs then ascend by u, then v, and a run of equal keys is as long as the uses of its edge
-//   heads / runs / entries   run heads, and behind the scan of the heads every run's first position; a run's length is the next run's first position
+//   heads / runs / entries   run heads, and behind the scan of the heads every run's first position (pass_dev.hpp's run kernels, launched by
+//              smooth_host.cpp); a run's length is the next run's first position
 //              less its own, so neighbours[] and uses[] are one gather per entry: no lane walks a run for this
 //   rows       one lane per vertex bisects the sorted keys for the position where its row begins (and the next row: its valence), reads the border
 //              flag the entries left, and has its class
@@ -12,8 +13,8 @@
 //              independent sums per lane
 //   incidence / normals   three (vertex, face) pairs per face that counts and is finite, one stable 32-bit pair sort by vertex, one lane per vertex
 //              walks its run in ascending face
-//   counters   integers (and one maximum of a double that is not negative, compared as bits), folded per wavefront, then per workgroup through LDS
-//              before one atomic each
+//   counters   integers (and one maximum of a double that is not negative, compared as bits), folded per workgroup before one atomic each
+//              (pass_dev.hpp's folds; the launches that count go over their items in a grid-stride loop, pd_grid_capped)
 // Integers, float bits and sequential double sums (compiled with -ffp-contract=off): the results do not depend on the order of anything.  Every
 // scatter index is checked against its room before the store.
 #include "smooth.hpp"
@@ -22,58 +23,6 @@
 #include "../../../include/immesh_smooth.h"
 
 namespace {
-
-// the launches that count go over their items in a grid-stride loop with at most SM_MAX_BLOCKS workgroups and keep their counts in registers
-constexpr int SM_MAX_BLOCKS = 1024;
-inline unsigned sm_grid(int64_t n) { return (unsigned)(tp_grid(n) < (unsigned)SM_MAX_BLOCKS ? tp_grid(n) : (unsigned)SM_MAX_BLOCKS); }
-
-__device__ __forceinline__ uint32_t sm_wave_sum(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// word += the workgroup's sum of v / word = max(word, the workgroup's largest v): every lane of the workgroup calls these, once, after its loop
-// (a lane's count stays below 2^31 / 2^18, a workgroup's below 2^31)
-__device__ __forceinline__ void sm_block_add(uint32_t v, unsigned long long* word, uint32_t* lds) {
-    v = sm_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < TP_BLOCK / 64; w++) t += lds[w];
-        if (t) atomicAdd(word, (unsigned long long)t);
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void sm_block_max(uint32_t v, unsigned long long* word, uint32_t* lds) {
-    v = tp_wave_max(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < TP_BLOCK / 64; w++) t = lds[w] > t ? lds[w] : t;
-        if (t) atomicMax(word, (unsigned long long)t);
-    }
-    __syncthreads();
-}
-// the same for a double that is neither negative nor NaN: such doubles order as their bits do
-__device__ __forceinline__ void sm_block_max_f64(double v, unsigned long long* word, double* lds) {
-    for (int m = 32; m >= 1; m >>= 1) { const double o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < TP_BLOCK / 64; w++) t = lds[w] > t ? lds[w] : t;
-        if (t > 0.0) atomicMax(word, (unsigned long long)__double_as_longlong(t));
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ bool sm_counts(int64_t a, int64_t b, int64_t c, int64_t n_vtx) {
-    return !(a < 0 || b < 0 || c < 0 || a >= n_vtx || b >= n_vtx || c >= n_vtx || a == b || b == c || a == c);
-}
-__device__ __forceinline__ bool sm_finite3(const float* __restrict__ vtx, int64_t v) {
-    return isfinite(vtx[3 * v]) && isfinite(vtx[3 * v + 1]) && isfinite(vtx[3 * v + 2]);
-}
 
 // the first position in [0, n) whose key is >= want (n: none)
 template <typename K>
@@ -98,7 +47,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_emit_kernel(const int32_t* __rest
     const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     const unsigned long long apart = (unsigned long long)n_vtx << 32;
     unsigned long long k[6] = {apart, apart, apart, apart, apart, apart};
-    if (sm_counts(a, b, c, n_vtx)) {
+    if (pd_counts(a, b, c, n_vtx)) {
         const unsigned long long ua = (unsigned long long)a, ub = (unsigned long long)b, uc = (unsigned long long)c;
         k[0] = (ua << 32) | ub; k[1] = (ub << 32) | ua;
         k[2] = (ub << 32) | uc; k[3] = (uc << 32) | ub;
@@ -107,25 +56,6 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_emit_kernel(const int32_t* __rest
     for (int e = 0; e < 6; e++) {
         key[6 * f + e] = k[e];
         val[6 * f + e] = (int32_t)(6 * f + e);
-    }
-}
-
-__global__ void __launch_bounds__(TP_BLOCK) sm_heads_kernel(const unsigned long long* __restrict__ key, int64_t n6, int32_t* __restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
-    if (i >= n6) return;
-    head[i] = i == 0 || key[i] != key[i - 1] ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(TP_BLOCK) sm_runs_kernel(int64_t n6, const int32_t* __restrict__ head, const int32_t* __restrict__ scan,
-                                                           int32_t* __restrict__ rstart) {
-    const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
-    if (i >= n6) return;
-    const int32_t h = head[i];
-    const int64_t p = scan[i];
-    if (h && p >= 0 && p < n6) rstart[p] = (int32_t)i;
-    if (i == n6 - 1) {
-        const int64_t runs = p + h;                             // (at most n6: rstart has n6 + 1 entries)
-        if (runs >= 0 && runs <= n6) rstart[runs] = (int32_t)n6;
     }
 }
 
@@ -160,7 +90,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_rows_kernel(const float* __restri
         if (v == n_vtx) { cnt[SM_N_PAIRS] = (unsigned long long)beg; continue; }   // the one writer
         const int64_t len = sm_runs_before(head, scan, n6, sm_lower_bound(key, n6, (unsigned long long)(v + 1) << 32)) - beg;
         int c = IMMESH_VERTEX_UNUSED;
-        if (len > 0) c = !sm_finite3(vtx, v) ? IMMESH_VERTEX_NOT_FINITE : flag[SM_FLAG_BORDER * n_vtx + v] ? IMMESH_VERTEX_BORDER : IMMESH_VERTEX_INTERIOR;
+        if (len > 0) c = !pd_finite3(vtx, v) ? IMMESH_VERTEX_NOT_FINITE : flag[SM_FLAG_BORDER * n_vtx + v] ? IMMESH_VERTEX_BORDER : IMMESH_VERTEX_INTERIOR;
         vclass[v] = (int8_t)c;
         n_used += c != IMMESH_VERTEX_UNUSED;
         n_not_finite += c == IMMESH_VERTEX_NOT_FINITE;
@@ -168,11 +98,11 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_rows_kernel(const float* __restri
         n_interior += c == IMMESH_VERTEX_INTERIOR;
         valence = (uint32_t)len > valence ? (uint32_t)len : valence;
     }
-    sm_block_add(n_used, cnt + SM_N_USED, lds);
-    sm_block_add(n_not_finite, cnt + SM_N_NOT_FINITE, lds);
-    sm_block_add(n_border, cnt + SM_N_BORDER, lds);
-    sm_block_add(n_interior, cnt + SM_N_INTERIOR, lds);
-    sm_block_max(valence, cnt + SM_MAX_VALENCE, lds);
+    pd_block_add(n_used, cnt + SM_N_USED, lds);
+    pd_block_add(n_not_finite, cnt + SM_N_NOT_FINITE, lds);
+    pd_block_add(n_border, cnt + SM_N_BORDER, lds);
+    pd_block_add(n_interior, cnt + SM_N_INTERIOR, lds);
+    pd_block_max(valence, cnt + SM_MAX_VALENCE, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sm_lists_kernel(const unsigned long long* __restrict__ key, int64_t n6, int64_t n_vtx,
@@ -235,7 +165,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_step_kernel(const float* __restri
         p_out[3 * v + 1] = r[1];
         p_out[3 * v + 2] = r[2];
     }
-    sm_block_add(n_held, cnt + SM_N_HELD, lds);
+    pd_block_add(n_held, cnt + SM_N_HELD, lds);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sm_finish_kernel(const float* __restrict__ p0, const float* __restrict__ pn, int64_t n_vtx,
@@ -257,9 +187,9 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_finish_kernel(const float* __rest
             disp2 = d2 > disp2 ? d2 : disp2;
         }
     }
-    sm_block_add(n_moving, cnt + SM_N_MOVING, lds);
-    sm_block_add(n_moved, cnt + SM_N_MOVED, lds);
-    sm_block_max_f64(disp2, cnt + SM_MAX_DISP2, lds_d);
+    pd_block_add(n_moving, cnt + SM_N_MOVING, lds);
+    pd_block_add(n_moved, cnt + SM_N_MOVED, lds);
+    pd_block_max_f64(disp2, cnt + SM_MAX_DISP2, lds_d);
 }
 
 __global__ void __launch_bounds__(TP_BLOCK) sm_incidence_kernel(const float* __restrict__ vtx, int64_t n_vtx, const int32_t* __restrict__ faces,
@@ -267,7 +197,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_incidence_kernel(const float* __r
     const int64_t f = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
     if (f >= n_faces) return;
     const int64_t i[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
-    const bool in = sm_counts(i[0], i[1], i[2], n_vtx) && sm_finite3(vtx, i[0]) && sm_finite3(vtx, i[1]) && sm_finite3(vtx, i[2]);
+    const bool in = pd_counts(i[0], i[1], i[2], n_vtx) && pd_finite3(vtx, i[0]) && pd_finite3(vtx, i[1]) && pd_finite3(vtx, i[2]);
     for (int e = 0; e < 3; e++) {
         key[3 * f + e] = in ? (uint32_t)i[e] : (uint32_t)n_vtx;
         val[3 * f + e] = (int32_t)f;
@@ -308,7 +238,7 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_normals_kernel(const float* __res
         normals[3 * v + 1] = o[1];
         normals[3 * v + 2] = o[2];
     }
-    sm_block_add(n_zero, cnt + SM_N_ZERO, lds);
+    pd_block_add(n_zero, cnt + SM_N_ZERO, lds);
 }
 
 }  // namespace
@@ -316,19 +246,13 @@ __global__ void __launch_bounds__(TP_BLOCK) sm_normals_kernel(const float* __res
 void sm_launch_emit(hipStream_t s, const int32_t* faces, int64_t n_faces, int64_t n_vtx, unsigned long long* key, int32_t* val) {
     if (n_faces > 0) sm_emit_kernel<<<tp_grid(n_faces), TP_BLOCK, 0, s>>>(faces, n_faces, n_vtx, key, val);
 }
-void sm_launch_heads(hipStream_t s, const unsigned long long* key, int64_t n6, int32_t* head) {
-    if (n6 > 0) sm_heads_kernel<<<tp_grid(n6), TP_BLOCK, 0, s>>>(key, n6, head);
-}
-void sm_launch_runs(hipStream_t s, int64_t n6, const int32_t* head, const int32_t* scan, int32_t* rstart) {
-    if (n6 > 0) sm_runs_kernel<<<tp_grid(n6), TP_BLOCK, 0, s>>>(n6, head, scan, rstart);
-}
 void sm_launch_entries(hipStream_t s, const unsigned long long* key, int64_t n6, int64_t n_vtx, const int32_t* head, const int32_t* scan, const int32_t* rstart,
                        int32_t* neighbours, int32_t* uses, int8_t* flag) {
     if (n6 > 0) sm_entries_kernel<<<tp_grid(n6), TP_BLOCK, 0, s>>>(key, n6, n_vtx, head, scan, rstart, neighbours, uses, flag);
 }
 void sm_launch_rows(hipStream_t s, const float* vtx, int64_t n_vtx, const unsigned long long* key, int64_t n6, const int32_t* head, const int32_t* scan,
                     const int8_t* flag, long long* row_start, int8_t* vclass, unsigned long long* cnt) {
-    if (n6 > 0 && n_vtx > 0) sm_rows_kernel<<<sm_grid(n_vtx + 1), TP_BLOCK, 0, s>>>(vtx, n_vtx, key, n6, head, scan, flag, row_start, vclass, cnt);
+    if (n6 > 0 && n_vtx > 0) sm_rows_kernel<<<pd_grid_capped(n_vtx + 1), TP_BLOCK, 0, s>>>(vtx, n_vtx, key, n6, head, scan, flag, row_start, vclass, cnt);
 }
 void sm_launch_lists(hipStream_t s, const unsigned long long* key, int64_t n6, int64_t n_vtx, const int32_t* head, const int32_t* scan, const int32_t* rstart,
                      const int32_t* neighbours, const int32_t* uses, const int8_t* vclass, int border, int32_t* sn, int8_t* flag) {
@@ -336,15 +260,15 @@ void sm_launch_lists(hipStream_t s, const unsigned long long* key, int64_t n6, i
 }
 void sm_launch_step(hipStream_t s, const float* p_in, float* p_out, int64_t n_vtx, const long long* row_start, const int32_t* sn, int64_t n6, double w,
                     unsigned long long* cnt) {
-    if (n_vtx > 0) sm_step_kernel<<<sm_grid(n_vtx), TP_BLOCK, 0, s>>>(p_in, p_out, n_vtx, row_start, sn, n6, w, cnt);
+    if (n_vtx > 0) sm_step_kernel<<<pd_grid_capped(n_vtx), TP_BLOCK, 0, s>>>(p_in, p_out, n_vtx, row_start, sn, n6, w, cnt);
 }
 void sm_launch_finish(hipStream_t s, const float* p0, const float* pn, int64_t n_vtx, const int8_t* flag, unsigned long long* cnt) {
-    if (n_vtx > 0) sm_finish_kernel<<<sm_grid(n_vtx), TP_BLOCK, 0, s>>>(p0, pn, n_vtx, flag, cnt);
+    if (n_vtx > 0) sm_finish_kernel<<<pd_grid_capped(n_vtx), TP_BLOCK, 0, s>>>(p0, pn, n_vtx, flag, cnt);
 }
 void sm_launch_incidence(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, uint32_t* key, int32_t* val) {
     if (n_faces > 0) sm_incidence_kernel<<<tp_grid(n_faces), TP_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, key, val);
 }
 void sm_launch_normals(hipStream_t s, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, const uint32_t* key, const int32_t* val,
                        float* normals, unsigned long long* cnt) {
-    if (n_vtx > 0) sm_normals_kernel<<<sm_grid(n_vtx), TP_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, key, val, normals, cnt);
+    if (n_vtx > 0) sm_normals_kernel<<<pd_grid_capped(n_vtx), TP_BLOCK, 0, s>>>(vtx, n_vtx, faces, n_faces, key, val, normals, cnt);
 }

@@ -18,11 +18,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t hl_wave_sum(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(TP_BLOCK) hl_init_kernel(int64_t n_vtx, const int32_t* __restrict__ vparent, int32_t* __restrict__ vt) {
     const int64_t v = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
     if (v >= n_vtx) return;
@@ -112,7 +107,7 @@ __global__ void __launch_bounds__(TP_BLOCK) hl_boxes_kernel(const float* __restr
         if (l >= n_loops) l = -1;
         for (int j = 0; j < 3; j++) {
             const float x = vtx[3 * v + j];
-            if (l >= 0 && isfinite(x)) lo[j] = hi[j] = tp_key(x);
+            if (l >= 0 && isfinite(x)) lo[j] = hi[j] = pd_key(x);
         }
     }
     // the fold of tp_components_kernel: one atomic per word, wavefront and loop for the first TP_FOLD_ROUNDS loops of the wavefront (the border of a
@@ -125,8 +120,8 @@ __global__ void __launch_bounds__(TP_BLOCK) hl_boxes_kernel(const float* __restr
         const unsigned long long m = __ballot(mine);
         uint32_t a[3], b[3];
         for (int j = 0; j < 3; j++) {
-            a[j] = tp_wave_min(mine ? lo[j] : TP_KEY_NONE_LO);
-            b[j] = tp_wave_max(mine ? hi[j] : TP_KEY_NONE_HI);
+            a[j] = pd_wave_min(mine ? lo[j] : TP_KEY_NONE_LO);
+            b[j] = pd_wave_max(mine ? hi[j] : TP_KEY_NONE_HI);
         }
         if ((int)(threadIdx.x & 63) == leader)
             for (int j = 0; j < 3; j++) {
@@ -171,7 +166,7 @@ __global__ void __launch_bounds__(TP_BLOCK) hl_limits_kernel(int64_t n_loops, in
             for (int j = 0; j < 3; j++) {
                 const uint32_t lo = box[6 * l + j], hi = box[6 * l + 3 + j];
                 have = have && lo != TP_KEY_NONE_LO && hi != TP_KEY_NONE_HI;
-                d[j] = (double)tp_unkey(hi) - (double)tp_unkey(lo);
+                d[j] = (double)pd_unkey(hi) - (double)pd_unkey(lo);
             }
             if (!have || (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] > max_diagonal * max_diagonal) status = IMMESH_HOLE_TOO_WIDE;
         }
@@ -220,8 +215,8 @@ __global__ void __launch_bounds__(TP_BLOCK) hl_decide_kernel(int64_t n_loops, in
     tp_count(in && status == IMMESH_HOLE_TOO_WIDE, cnt + HC_N_TOO_WIDE);
     tp_count(in && status == IMMESH_HOLE_BLOCKED, cnt + HC_N_BLOCKED);
     tp_count(filled, cnt + HC_N_FILLED);
-    const uint32_t closed = hl_wave_sum(filled ? (uint32_t)n : 0u);   // (a wavefront's loops have fewer than 2^31 - 2 boundary edges together)
-    const uint32_t largest = tp_wave_max(simple ? (uint32_t)n : 0u);
+    const uint32_t closed = pd_wave_sum(filled ? (uint32_t)n : 0u);   // (a wavefront's loops have fewer than 2^31 - 2 boundary edges together)
+    const uint32_t largest = pd_wave_max(simple ? (uint32_t)n : 0u);
     if ((threadIdx.x & 63) == 0) {
         if (closed) atomicAdd(cnt + HC_N_CLOSED, (unsigned long long)closed);
         if (largest) atomicMax(cnt + HC_LARGEST_SIMPLE, (unsigned long long)largest);

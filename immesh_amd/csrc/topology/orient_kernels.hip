@@ -44,11 +44,6 @@ __device__ __forceinline__ void ot_fold(int32_t c, const bool (&p)[N], int32_t* 
             if (p[j]) atomicAdd(tab[j] + c, 1);
 }
 
-__device__ __forceinline__ uint32_t ot_wave_sum(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // the contract's sign of face (ia, ib, ic) about the viewpoint o: immesh_closest.h's side rule with p = o
 __device__ __forceinline__ int ot_sign(const float* __restrict__ vtx, int64_t ia, int64_t ib, int64_t ic, const OtPoint& o) {
     double A[3][3];
@@ -175,7 +170,7 @@ __global__ void __launch_bounds__(TP_BLOCK) ot_decide_kernel(int64_t n_bound, in
     tp_count(in && orientable, cnt + OT_N_ORIENTABLE);
     tp_count(in && !orientable, cnt + OT_N_NONORIENTABLE);
     tp_count(invert, cnt + OT_N_INVERTED);
-    const uint32_t largest = tp_wave_max(n), f_sum = ot_wave_sum(flipped), n_sum = ot_wave_sum(in && !orientable ? n : 0u), i_sum = ot_wave_sum(inconsistent);
+    const uint32_t largest = pd_wave_max(n), f_sum = pd_wave_sum(flipped), n_sum = pd_wave_sum(in && !orientable ? n : 0u), i_sum = pd_wave_sum(inconsistent);
     if ((threadIdx.x & 63) == 0) {
         if (largest) atomicMax(cnt + OT_LARGEST_PATCH, (unsigned long long)largest);
         if (f_sum) atomicAdd(cnt + OT_N_FLIPPED, (unsigned long long)f_sum);

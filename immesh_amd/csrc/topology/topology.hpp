@@ -51,10 +51,7 @@ void tp_launch_boundary(hipStream_t s, const unsigned long long* key, const int3
 void tp_launch_largest(hipStream_t s, const int32_t* root, const int32_t* num, const int32_t* nfaces, int64_t n_faces, unsigned long long* cnt);
 
 // edge lists ------------------------------------------------------------------------------------------------------------------------------
-// head[i] = 1 for a run head of the sorted keys
-void tp_launch_heads(hipStream_t s, const unsigned long long* key, int64_t n_half, int32_t* head);
-// start[e] = the position of edge e's head (e = eid[i], the exclusive prefix sum of head), start[n_edges] = n_half
-void tp_launch_starts(hipStream_t s, const int32_t* head, const int32_t* eid, int64_t n_half, int64_t n_edges, int32_t* start);
+// (head[i] = 1 for a run head of the sorted keys, start[e] = the position of edge e's head, start[n_edges] = n_half: raycast/pass_dev.hpp's run kernels)
 // pick[e] = 1 when edge e is of `kind`
 void tp_launch_pick(hipStream_t s, const int32_t* start, int64_t n_edges, const int32_t* val, const int32_t* faces, int32_t kind, int32_t* pick);
 // the picked edges, in order: uv[2 j], uses[j]

@@ -3,10 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "../raycast/pass_dev.hpp"   // the folds, the float keys, the rule "a face counts", the run kernels: shared with the other passes
 
 namespace {
 
 constexpr int TP_BLOCK = 256;
+static_assert(TP_BLOCK == RC_BLOCK, "the shared folds of pass_dev.hpp are written for workgroups of RC_BLOCK");
 constexpr int TP_FOLD_ROUNDS = 4;   // components / patches folded per wavefront before the lanes left over send their own atomics
 inline unsigned tp_grid(int64_t n) { return (unsigned)((n + TP_BLOCK - 1) / TP_BLOCK); }
 
@@ -15,13 +17,6 @@ __device__ __forceinline__ void tp_count(bool pred, unsigned long long* word) {
     const unsigned long long m = __ballot(pred);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(word, (unsigned long long)__popcll(m));
 }
-
-// box keys: order-preserving, as rc_compact_kernel's (topology.hpp has the presets)
-__device__ __forceinline__ uint32_t tp_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tp_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // ---- union-find ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t tp_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -61,15 +56,6 @@ __device__ __forceinline__ bool tp_forward(const int32_t* __restrict__ faces, in
     const int64_t f = h / 3;
     const int k = h - 3 * (int32_t)f;
     return faces[3 * f + k] < faces[3 * f + (k == 2 ? 0 : k + 1)];
-}
-
-__device__ __forceinline__ uint32_t tp_wave_min(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t tp_wave_max(uint32_t v) {
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
-    return v;
 }
 
 }  // namespace

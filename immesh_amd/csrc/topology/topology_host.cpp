@@ -8,6 +8,7 @@
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_topology.h"
 #include "topology.hpp"
+#include "../raycast/pass_dev.hpp"   // the run kernels of the edge lists
 
 static_assert(sizeof(immesh_topology_stats) == 14 * 8 && offsetof(immesh_topology_stats, n_faces) == 0 && offsetof(immesh_topology_stats, n_counting) == 8 &&
                   offsetof(immesh_topology_stats, n_degenerate) == 16 && offsetof(immesh_topology_stats, n_vertices_used) == 24 &&
@@ -182,9 +183,9 @@ int immesh_topology_edges(immesh_raycaster* r, int32_t kind, int32_t* uv, int32_
     if ((rc = tp_grow(r, q.uses, (size_t)n * 4))) return rc;
     const unsigned long long* key = (const unsigned long long*)q.key_b.p;
     int32_t *head = (int32_t*)q.head.p, *eid = (int32_t*)q.eid.p, *start = (int32_t*)q.start.p, *pick = (int32_t*)q.pick.p, *poff = (int32_t*)q.poff.p;
-    tp_launch_heads(s, key, n_half, head);
+    pd_launch_run_heads(s, key, n_half, head);
     exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, head, eid, (int)n_half);
-    tp_launch_starts(s, head, eid, n_half, n_edges, start);
+    pd_launch_run_starts(s, n_half, head, eid, start, n_edges + 1);
     tp_launch_pick(s, start, n_edges, (const int32_t*)q.val_b.p, (const int32_t*)r->faces.p, kind, pick);
     exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, pick, poff, (int)n_edges);
     tp_launch_edges(s, start, n_edges, key, pick, poff, (int32_t*)q.uv.p, (int32_t*)q.uses.p);

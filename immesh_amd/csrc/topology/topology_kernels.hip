@@ -15,7 +15,7 @@
 //   boundary   the boundary heads once more, now that the components are numbered: boundary edges per component, edges per loop
 // All of it integers and min / max: the results do not depend on the order of anything.
 #include "topology.hpp"
-#include "topology_dev.hpp"   // the union-find, the ballot counts, the wavefront folds, the box keys: the orientation's and the holes' kernels use them too
+#include "topology_dev.hpp"   // the union-find and the ballot counts (the orientation's and the holes' kernels use them too), and with it raycast/pass_dev.hpp
 
 namespace {
 
@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_mark_kernel(const int32_t* __rest
     if (f >= n_faces) return;
     const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     // (both build calls give indices in range; a face with one out of range would not count, so that nothing below indexes outside its arrays)
-    const bool ok = a != b && b != c && a != c && a >= 0 && b >= 0 && c >= 0 && a < n_vtx && b < n_vtx && c < n_vtx;
+    const bool ok = pd_counts(a, b, c, n_vtx);
     flag[f] = ok ? 1 : 0;
     parent[f] = (int32_t)f;
     if (ok) { used[a] = 1; used[b] = 1; used[c] = 1; }
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_components_kernel(const float* __
                 for (int j = 0; j < 3; j++) {
                     const float x = v[j];
                     if (isfinite(x)) {
-                        const uint32_t q = tp_key(x);
+                        const uint32_t q = pd_key(x);
                         lo[j] = q < lo[j] ? q : lo[j];
                         hi[j] = q > hi[j] ? q : hi[j];
                     }
@@ -140,8 +140,8 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_components_kernel(const float* __
         const unsigned long long m = __ballot(mine);
         uint32_t l[3], h[3];
         for (int j = 0; j < 3; j++) {
-            l[j] = tp_wave_min(mine ? lo[j] : TP_KEY_NONE_LO);
-            h[j] = tp_wave_max(mine ? hi[j] : TP_KEY_NONE_HI);
+            l[j] = pd_wave_min(mine ? lo[j] : TP_KEY_NONE_LO);
+            h[j] = pd_wave_max(mine ? hi[j] : TP_KEY_NONE_HI);
         }
         if ((int)(threadIdx.x & 63) == leader) {
             atomicAdd(nfaces + c0, (int32_t)__popcll(m));
@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_boundary_kernel(const unsigned lo
         }
     }
     tp_count(opened, cnt + TP_N_LOOPS);
-    edges = tp_wave_max(edges);                              // the largest count any lane saw is the largest loop's final count
+    edges = pd_wave_max(edges);                              // the largest count any lane saw is the largest loop's final count
     if ((threadIdx.x & 63) == 0 && edges) atomicMax(cnt + TP_LARGEST_LOOP, (unsigned long long)edges);
 }
 
@@ -188,24 +188,11 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_largest_kernel(const int32_t* __r
     const int64_t f = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
     uint32_t n = 0;
     if (f < n_faces && root[f]) n = (uint32_t)nfaces[num[f]];
-    n = tp_wave_max(n);
+    n = pd_wave_max(n);
     if ((threadIdx.x & 63) == 0 && n) atomicMax(cnt + TP_LARGEST_COMPONENT, (unsigned long long)n);
 }
 
-// ---- edge lists -----------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(TP_BLOCK) tp_heads_kernel(const unsigned long long* __restrict__ key, int64_t n_half, int32_t* __restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
-    if (i < n_half) head[i] = (i == 0 || key[i - 1] != key[i]) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(TP_BLOCK) tp_starts_kernel(const int32_t* __restrict__ head, const int32_t* __restrict__ eid, int64_t n_half, int64_t n_edges,
-                                                             int32_t* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
-    if (i >= n_half) return;
-    if (head[i]) start[eid[i]] = (int32_t)i;
-    if (i == 0) start[n_edges] = (int32_t)n_half;
-}
-
+// ---- edge lists (the run heads and run starts are pass_dev.hpp's, launched by topology_host.cpp) -----------------------------------------------
 __global__ void __launch_bounds__(TP_BLOCK) tp_pick_kernel(const int32_t* __restrict__ start, int64_t n_edges, const int32_t* __restrict__ val,
                                                            const int32_t* __restrict__ faces, int32_t kind, int32_t* __restrict__ pick) {
     const int64_t e = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
@@ -252,7 +239,7 @@ __global__ void __launch_bounds__(TP_BLOCK) tp_decide_kernel(const int32_t* __re
         for (int j = 0; j < 3; j++) {
             const uint32_t lo = box[6 * c + j], hi = box[6 * c + 3 + j];
             have = have && lo != TP_KEY_NONE_LO && hi != TP_KEY_NONE_HI;
-            d[j] = (double)tp_unkey(hi) - (double)tp_unkey(lo);
+            d[j] = (double)pd_unkey(hi) - (double)pd_unkey(lo);
         }
         keep = keep && have && (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] >= min_diagonal * min_diagonal;
     }
@@ -314,12 +301,6 @@ void tp_launch_largest(hipStream_t s, const int32_t* root, const int32_t* num, c
     if (n_faces > 0) tp_largest_kernel<<<tp_grid(n_faces), TP_BLOCK, 0, s>>>(root, num, nfaces, n_faces, cnt);
 }
 
-void tp_launch_heads(hipStream_t s, const unsigned long long* key, int64_t n_half, int32_t* head) {
-    if (n_half > 0) tp_heads_kernel<<<tp_grid(n_half), TP_BLOCK, 0, s>>>(key, n_half, head);
-}
-void tp_launch_starts(hipStream_t s, const int32_t* head, const int32_t* eid, int64_t n_half, int64_t n_edges, int32_t* start) {
-    if (n_half > 0) tp_starts_kernel<<<tp_grid(n_half), TP_BLOCK, 0, s>>>(head, eid, n_half, n_edges, start);
-}
 void tp_launch_pick(hipStream_t s, const int32_t* start, int64_t n_edges, const int32_t* val, const int32_t* faces, int32_t kind, int32_t* pick) {
     if (n_edges > 0) tp_pick_kernel<<<tp_grid(n_edges), TP_BLOCK, 0, s>>>(start, n_edges, val, faces, kind, pick);
 }
