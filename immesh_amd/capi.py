@@ -173,6 +173,77 @@ class ClosestStats(C.Structure):
                 ("max_dist", C.c_float), ("bin_width", C.c_float)]
 
 
+class AlignOptions(C.Structure):
+    """immesh_align_options (include/immesh_align.h)"""
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("max_dist", C.c_double), ("centre", C.c_double * 3), ("damping", C.c_double),
+                ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
+class AlignSystem(C.Structure):
+    """immesh_align_system (include/immesh_align.h): the 28 sums of a step (H a <= b row by row, g, e) and its four counts"""
+    _fields_ = [("H", C.c_double * 21), ("g", C.c_double * 6), ("e", C.c_double),
+                ("n_used", C.c_int64), ("n_not_finite", C.c_int64), ("n_no_face", C.c_int64), ("n_flat", C.c_int64)]
+
+    def sums(self):
+        """the 28 sums in the terms' order -> (28,) float64"""
+        return np.array(list(self.H) + list(self.g) + [self.e], np.float64)
+
+    def counts(self):
+        return self.n_used, self.n_not_finite, self.n_no_face, self.n_flat
+
+
+class AlignResult(C.Structure):
+    """immesh_align_result (include/immesh_align.h)"""
+    _fields_ = [("frame", RayFrame), ("status", C.c_int32), ("iterations", C.c_int32), ("system", AlignSystem), ("rms", C.c_double)]
+
+
+assert (C.sizeof(AlignOptions), C.sizeof(AlignSystem), C.sizeof(AlignResult)) == (64, 256, 368)
+ALIGN_POINT, ALIGN_PLANE = 0, 1
+ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = 0, 1, 2, 3
+ALIGN_STATUS = ("converged", "max_iters", "too_few", "degenerate")
+ALIGN_TERMS = 28
+
+
+def align_options(mode=ALIGN_POINT, max_dist=1.0, centre=(0.0, 0.0, 0.0), damping=0.0, max_iters=30, eps_rot=1e-9, eps_trans=1e-9):
+    """an AlignOptions (the defaults are immesh_align_default_options'); centre: three numbers (align() also takes "mean")"""
+    o = AlignOptions(mode=mode, max_iters=max_iters, max_dist=max_dist, damping=damping, eps_rot=eps_rot, eps_trans=eps_trans)
+    o.centre[:] = [float(x) for x in centre]
+    return o
+
+
+def align_centre_mean(pts, frame=None):
+    """the mean of the finite points under `frame` (None: as they are), in float64 -> [x, y, z]; zeros without a finite point"""
+    p = np.asarray(pts, np.float32).reshape(-1, 3)
+    p = p[np.isfinite(p).all(axis=1)].astype(np.float64)
+    if len(p) == 0:
+        return [0.0, 0.0, 0.0]
+    m = p.mean(axis=0)
+    if frame is not None:
+        m = np.array(list(frame.rot)).reshape(3, 3) @ m + np.array(list(frame.pos))
+    return [float(x) for x in m]
+
+
+def align_solve(lib, system, damping=0.0):
+    """immesh_align_solve (pure host code, no context) -> (degenerate, delta (6,) float64)"""
+    f = lib.immesh_align_solve; f.argtypes = [C.POINTER(AlignSystem), C.c_double, C.c_void_p]; f.restype = C.c_int
+    delta = np.zeros(6, np.float64)
+    rc = f(C.byref(system), damping, _ptr(delta))
+    if rc not in (0, 1):
+        raise RuntimeError(f"immesh_align_solve failed rc={rc}")
+    return rc == 1, delta
+
+
+def align_update(lib, frame, centre, delta):
+    """immesh_align_update (pure host code, no context) -> RayFrame"""
+    f = lib.immesh_align_update; f.argtypes = [C.POINTER(RayFrame), C.c_void_p, C.c_void_p, C.POINTER(RayFrame)]; f.restype = C.c_int
+    ce, d = np.ascontiguousarray(centre, dtype=np.float64).reshape(3), np.ascontiguousarray(delta, dtype=np.float64).reshape(6)
+    out = RayFrame()
+    rc = f(C.byref(frame), _ptr(ce), _ptr(d), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"immesh_align_update failed rc={rc}")
+    return out
+
+
 class TopologyStats(C.Structure):
     """immesh_topology_stats (include/immesh_topology.h): the counts of the last analysis of the caster's snapshot"""
     _fields_ = [(n, C.c_int64) for n in ("n_faces", "n_counting", "n_degenerate", "n_vertices_used", "n_edges", "n_boundary", "n_interior", "n_nonmanifold",
@@ -856,6 +927,55 @@ class HotPath:
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "closest_last_timing")
         return float(ms[0]), float(ms[1])
+
+    # -- align a cloud to the caster's snapshot (include/immesh_align.h) -----------------------------------------------------------------------------
+    def align_step(self, pts, opts, frame=None, want_face=False, want_terms=False):
+        """immesh_align_step: one step at `frame` (None: world coordinates) -> (AlignSystem, face (n,) int32 or None, terms (n, 28) float64 or None)"""
+        f = self.lib.immesh_align_step
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.POINTER(AlignOptions), C.POINTER(AlignSystem), C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        face = np.empty(len(p), np.int32) if want_face else None
+        terms = np.empty((len(p), ALIGN_TERMS), np.float64) if want_terms else None
+        sy = AlignSystem()
+        self._check(f(self.raycaster(), None if frame is None else C.byref(frame), _ptr(p), len(p), C.byref(opts), C.byref(sy), _ptr(face), _ptr(terms)),
+                    "align_step")
+        return sy, face, terms
+
+    def align_solve(self, system, damping=0.0):
+        return align_solve(self.lib, system, damping)
+
+    def align_update(self, frame, centre, delta):
+        return align_update(self.lib, frame, centre, delta)
+
+    def align(self, pts, opts=None, frame=None, centre=None, history_cap=None, **over):
+        """immesh_align: the loop from `frame` (None: the identity) -> (AlignResult, history (iterations, 4) float64: n_used, rms, |omega|, |v|).
+        opts: an AlignOptions, or None for align_options(**over); centre "mean": the mean of the finite points under `frame`, computed here in float64."""
+        f = self.lib.immesh_align
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.POINTER(AlignOptions), C.POINTER(AlignResult), C.c_void_p, C.c_int64]
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        o = align_options(**over) if opts is None else opts
+        if centre is not None:
+            o = AlignOptions.from_buffer_copy(o)
+            o.centre[:] = align_centre_mean(p, frame) if isinstance(centre, str) and centre == "mean" else [float(x) for x in centre]
+        cap = max(0, min(int(o.max_iters), 10000)) if history_cap is None else history_cap
+        hist = np.zeros((cap, 4), np.float64)
+        res = AlignResult()
+        self._check(f(self.raycaster(), None if frame is None else C.byref(frame), _ptr(p), len(p), C.byref(o), C.byref(res), _ptr(hist), cap), "align")
+        return res, hist[:min(res.iterations, cap)]
+
+    def align_timing(self):
+        """device milliseconds of (the last step, the sum over the last loop's steps)"""
+        f = self.lib.immesh_align_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "align_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def align_set_variant(self, variant):
+        """immesh_align_set_variant: 0 the fused step (the default), 1 split, 2 fused without the register cap (for measurements; the same bits)"""
+        f = self.lib.immesh_align_set_variant; f.argtypes = [C.c_void_p, C.c_int32]; f.restype = C.c_int
+        self._check(f(self.raycaster(), variant), "align_set_variant")
 
     # -- mesh-to-cloud distances (include/immesh_nearest.h) ------------------------------------------------------------------------------------------
     def cloud_index(self):

@@ -144,6 +144,30 @@ struct RcClosest {
     ~RcClosest() { rc_destroy_events(ev, 4); }
 };
 
+// one partial of an alignment step's fold, and the folded system (include/immesh_align.h): the 28 sums in the header's order, then n_used,
+// n_not_finite, n_no_face, n_flat
+struct AlSystemDev {
+    double s[28];
+    int64_t n[4];
+};
+static_assert(sizeof(AlSystemDev) == 256, "AlSystemDev layout");
+
+// alignment of a cloud to the snapshot (include/immesh_align.h; align/align_host.cpp): allocated at the first step, never before.  Its buffers, events
+// and pinned words are its own: the last closest query's results stay as they are across an alignment.
+struct RcAlign {
+    hipEvent_t ev[2] = {nullptr, nullptr};                     // a step: begin / end
+    RcBuf pts, part, res;                                      // the cloud; per-workgroup partials; the folded system
+    RcBuf face, terms;                                         // per point, only when asked for
+    RcBuf sface, sq;                                           // the split variant's face and q per point
+    AlSystemDev* h_res = nullptr;                              // pinned
+    int variant = 0;                                           // 0 fused (registers capped), 1 split, 2 fused, not capped
+    float ms[2] = {0.0f, 0.0f};
+    ~RcAlign() {
+        rc_destroy_events(ev, 2);
+        if (h_res) (void)hipHostFree(h_res);
+    }
+};
+
 // samples of the snapshot (include/immesh_nearest.h): allocated at the first immesh_mesh_sample, never before
 struct RcSample {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // counts, scan + emit: begin / end
@@ -263,6 +287,7 @@ struct immesh_raycaster {
     int64_t n_points = 0;
     float ms[3] = {0.0f, 0.0f, 0.0f};
     RcClosest cl;
+    RcAlign al;
     RcSample sm;
     RcTopology tp;
     RcOrient ot;

@@ -1,4 +1,4 @@
-// Device helpers shared by the kernels on the caster's hierarchy: raycast_kernels.hip, closest_kernels.hip, nearest_kernels.hip.
+// Device helpers shared by the kernels on the caster's hierarchy: raycast_kernels.hip, closest_kernels.hip, nearest_kernels.hip, align/align_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -47,6 +47,48 @@ __device__ __forceinline__ double dq_box(const double* p, const float* lo, const
     double e[3];
     for (int k = 0; k < 3; k++) e[k] = fmax(fmax((double)lo[k] - p[k], p[k] - (double)hi[k]), 0.0);
     return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
+__device__ __forceinline__ double rc_unit(double x) { return x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0; }   // held to [0, 1]; NaN -> 0
+
+// the closest-point contract's Face rule (the closest query and the alignment step share it): q, the closest point of the face (a, b, c relative to the query) by the region method
+__device__ __forceinline__ void rc_face_point(const double* a, const double* b, const double* c, double* q) {
+    double ab[3], ac[3], ma[3], mb[3], mc[3];
+    for (int k = 0; k < 3; k++) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; ma[k] = -a[k]; mb[k] = -b[k]; mc[k] = -c[k]; }
+    const double d1 = rc_dot(ab, ma), d2 = rc_dot(ac, ma);
+    if (d1 <= 0.0 && d2 <= 0.0) { q[0] = a[0]; q[1] = a[1]; q[2] = a[2]; return; }
+    const double d3 = rc_dot(ab, mb), d4 = rc_dot(ac, mb);
+    if (d3 >= 0.0 && d4 <= d3) { q[0] = b[0]; q[1] = b[1]; q[2] = b[2]; return; }
+    const double vc = d1 * d4 - d3 * d2;
+    const double den_ab = d1 - d3;
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0 && den_ab != 0.0) {
+        const double v = rc_unit(d1 / den_ab);
+        for (int k = 0; k < 3; k++) q[k] = a[k] + v * ab[k];
+        return;
+    }
+    const double d5 = rc_dot(ab, mc), d6 = rc_dot(ac, mc);
+    if (d6 >= 0.0 && d5 <= d6) { q[0] = c[0]; q[1] = c[1]; q[2] = c[2]; return; }
+    const double vb = d5 * d2 - d1 * d6;
+    const double den_ac = d2 - d6;
+    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0 && den_ac != 0.0) {
+        const double w = rc_unit(d2 / den_ac);
+        for (int k = 0; k < 3; k++) q[k] = a[k] + w * ac[k];
+        return;
+    }
+    const double va = d3 * d6 - d5 * d4;
+    const double e43 = d4 - d3, e56 = d5 - d6;
+    const double den_bc = e43 + e56;
+    if (va <= 0.0 && e43 >= 0.0 && e56 >= 0.0 && den_bc != 0.0) {
+        const double w = rc_unit(e43 / den_bc);
+        for (int k = 0; k < 3; k++) q[k] = b[k] + w * (c[k] - b[k]);
+        return;
+    }
+    const double sum = (va + vb) + vc;
+    const double inv = sum != 0.0 ? 1.0 / sum : 0.0;
+    const double v = rc_unit(vb * inv);
+    const double w1 = rc_unit(vc * inv), rest = 1.0 - v;
+    const double w = w1 < rest ? w1 : rest;
+    for (int k = 0; k < 3; k++) q[k] = (a[k] + ab[k] * v) + ac[k] * w;
 }
 
 __device__ __forceinline__ float dq_round_down(double x) {   // x >= 0: the largest float <= x

@@ -39,6 +39,12 @@ include/immesh_intersect.h), all off by default:
   --self-intersections [--max-candidates N]
                             the self-intersection counts of the mesh that is evaluated, after every other clean-up option, in an `intersections`
                             block.  N bounds the candidate pairs of either option (2^24 by default): a mesh with more is refused
+One option looks at the cloud first (include/immesh_align.h), off by default:
+  --align point|plane [--align-max-dist D] [--align-iters N]
+                            after every option above and before anything else reads the cloud: refine the cloud's pose against the mesh that is
+                            evaluated by iterated closest-face least squares (immesh_align) from the identity, linearised about the cloud's mean, with
+                            point or point-to-plane rows, pairs within D (1.0), at most N iterations (30), and move the cloud by the pose found.  The
+                            output gains an `align` block: the options, status, iterations, pose and the rms per iteration
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
@@ -48,6 +54,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--weld | --simplify CELL [--simplify-mode first|mean]] [--keep-duplicate-faces]
                               [--smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]]
                               [--remove-self-intersections] [--self-intersections] [--max-candidates N]
+                              [--align point|plane [--align-max-dist D] [--align-iters N]]
 """
 import argparse
 import json
@@ -189,6 +196,22 @@ def topology(h):
     return {n: getattr(st, n) for n, _ in capi.TopologyStats._fields_}
 
 
+ALIGN_MODES = {"point": capi.ALIGN_POINT, "plane": capi.ALIGN_PLANE}
+
+
+def align_cloud(h, cloud, mode, max_dist=1.0, max_iters=30):
+    """h: a HotPath with a built caster -> (the cloud moved by the pose that the alignment finds from the identity, linearised about the cloud's mean;
+    the options, status, iterations, pose and the rms per iteration)"""
+    cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    centre = capi.align_centre_mean(cloud)
+    res, hist = h.align(cloud, capi.align_options(mode=ALIGN_MODES[mode], max_dist=max_dist, centre=centre, max_iters=max_iters))
+    rot, pos = np.array(list(res.frame.rot)).reshape(3, 3), np.array(list(res.frame.pos))
+    moved = (cloud.astype(np.float64) @ rot.T + pos).astype(np.float32)
+    return moved, {"mode": mode, "max_dist": max_dist, "max_iters": max_iters, "centre": centre, "status": capi.ALIGN_STATUS[res.status],
+                   "iterations": res.iterations, "rot": rot.reshape(-1).tolist(), "pos": pos.tolist(), "points_used": [int(v) for v in hist[:, 0]],
+                   "rms": hist[:, 1].tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cloud", required=True, help="ground-truth points, .npy of shape (n, 3) or (n, >= 3)")
@@ -215,7 +238,12 @@ def main():
     ap.add_argument("--remove-self-intersections", action="store_true", help="take the faces that pass through each other out, right after --weld / --simplify")
     ap.add_argument("--self-intersections", action="store_true", help="add the evaluated mesh's self-intersection counts to the output")
     ap.add_argument("--max-candidates", type=int, default=None, metavar="N", help="with either of the two: refuse a mesh with more candidate pairs (2^24)")
+    ap.add_argument("--align", choices=sorted(ALIGN_MODES), default=None, help="refine the cloud's pose against the evaluated mesh first (ICP with point or plane rows)")
+    ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="with --align: pairs farther apart do not take part (1.0)")
+    ap.add_argument("--align-iters", type=int, default=None, metavar="N", help="with --align: at most N iterations (30)")
     args = ap.parse_args()
+    if args.align is None and (args.align_max_dist is not None or args.align_iters is not None):
+        ap.error("--align-max-dist and --align-iters go with --align {point,plane}")
     if args.max_candidates is not None and not (args.remove_self_intersections or args.self_intersections):
         ap.error("--max-candidates N goes with --remove-self-intersections or --self-intersections")
     max_candidates = (1 << 24) if args.max_candidates is None else args.max_candidates
@@ -254,6 +282,9 @@ def main():
             extra["topology"] = topology(h)
         if args.self_intersections:
             extra["intersections"] = self_intersections(h, max_candidates)
+        if args.align:                                    # the cloud is moved before anything else reads it
+            cloud, extra["align"] = align_cloud(h, cloud, args.align, 1.0 if args.align_max_dist is None else args.align_max_dist,
+                                                30 if args.align_iters is None else args.align_iters)
         out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
                    **extra)
     finally:
