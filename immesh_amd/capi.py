@@ -275,6 +275,16 @@ assert C.sizeof(HolesStats) == 96
 HOLE_FILLED, HOLE_NONSIMPLE, HOLE_OUTLINE, HOLE_TOO_LONG, HOLE_TOO_WIDE, HOLE_BLOCKED = 0, 1, 2, 3, 4, 5
 
 
+class ManifoldStats(C.Structure):
+    """immesh_manifold_stats (include/immesh_topology.h): the counts of the last manifold pass over the analysed snapshot"""
+    _fields_ = [(n, C.c_int64) for n in ("n_corners", "n_fans", "n_vertices_used", "n_singular_vertices", "most_fans_at_vertex", "n_new_vertices",
+                                         "n_corners_moved", "n_faces_changed", "n_closed_fans", "n_open_fans", "largest_fan_corners",
+                                         "n_nonmanifold_before")]
+
+
+assert C.sizeof(ManifoldStats) == 96
+
+
 class SimplifyStats(C.Structure):
     """immesh_simplify_stats (include/immesh_simplify.h): the counts of the last weld / clustering pass over the caster's snapshot"""
     _fields_ = [(n, C.c_int64) for n in ("n_vertices_in", "n_vertices_used", "n_alone_not_finite", "n_alone_outside", "n_vertices_out", "largest_cluster",
@@ -1206,6 +1216,63 @@ class HotPath:
         f = self.lib.immesh_topology_holes_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
         ms = (C.c_float * 2)()
         self._check(f(self.raycaster(), ms), "topology_holes_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def topology_manifold(self):
+        """immesh_topology_manifold on the analysed snapshot: every fan of faces round a vertex gets a vertex of its own -> ManifoldStats; the pass
+        stays on the device for the calls below"""
+        f = self.lib.immesh_topology_manifold; f.argtypes = [C.c_void_p, C.POINTER(ManifoldStats)]; f.restype = C.c_int
+        st = ManifoldStats()
+        self._check(f(self.raycaster(), C.byref(st)), "topology_manifold")
+        return st
+
+    def topology_manifold_vertices(self):
+        """-> n_fans_out (n_vtx,) int32: the fans at every vertex, 0 for an unused one"""
+        f = self.lib.immesh_topology_manifold_vertices; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster(), None), "topology_manifold_vertices")
+        out = np.empty(self._raycast_sizes()[0], np.int32)
+        self._check(f(self.raycaster(), _ptr(out)), "topology_manifold_vertices")
+        return out
+
+    def topology_manifold_fans(self):
+        """the fan tables -> dict: vertex, first_face, n_corners, n_links, index_out (n_fans,) int32"""
+        f = self.lib.immesh_topology_manifold_fans; f.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, None, None, None, 0, C.byref(n)), "topology_manifold_fans")
+        names = ("vertex", "first_face", "n_corners", "n_links", "index_out")
+        out = {k: np.empty(n.value, np.int32) for k in names}
+        self._check(f(self.raycaster(), *[_ptr(out[k]) for k in names], n.value, C.byref(n)), "topology_manifold_fans")
+        return out
+
+    def topology_manifold_faces(self):
+        """-> (fan_out (n_faces, 3) int32, -1 for the corners of a face that does not count; faces_out (n_faces, 3) int32)"""
+        f = self.lib.immesh_topology_manifold_faces; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster(), None, None), "topology_manifold_faces")
+        nf = self._raycast_sizes()[1]
+        fan, faces = np.empty((nf, 3), np.int32), np.empty((nf, 3), np.int32)
+        self._check(f(self.raycaster(), _ptr(fan), _ptr(faces)), "topology_manifold_faces")
+        return fan, faces
+
+    def topology_manifold_new_vertices(self):
+        """the new vertices -> (vsrc (n,) int32, xyz (n, 3) float32: the bits of their sources)"""
+        f = self.lib.immesh_topology_manifold_new_vertices; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.raycaster(), None, None, 0, C.byref(n)), "topology_manifold_new_vertices")
+        vsrc, xyz = np.empty(n.value, np.int32), np.empty((n.value, 3), np.float32)
+        self._check(f(self.raycaster(), _ptr(vsrc), _ptr(xyz), n.value, C.byref(n)), "topology_manifold_new_vertices")
+        return vsrc, xyz
+
+    def topology_manifold_apply(self):
+        """immesh_topology_manifold_apply: vtx_out and faces_out become the caster's, on the device, and its hierarchy is built again; everything a
+        build discards is discarded"""
+        f = self.lib.immesh_topology_manifold_apply; f.argtypes = [C.c_void_p]; f.restype = C.c_int
+        self._check(f(self.raycaster()), "topology_manifold_apply")
+
+    def topology_manifold_timing(self):
+        """device milliseconds of the last (manifold pass, apply)"""
+        f = self.lib.immesh_topology_manifold_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.raycaster(), ms), "topology_manifold_last_timing")
         return float(ms[0]), float(ms[1])
 
     # -- weld and vertex clustering of the caster's snapshot (include/immesh_simplify.h) ---------------------------------------------------------------

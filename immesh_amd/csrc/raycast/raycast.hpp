@@ -184,9 +184,9 @@ struct RcSample {
     }
 };
 
-// What the six passes over the snapshot share (analysis, orientation, holes, simplification, smoothing, self-intersections): the events of their spans, the device
+// What the seven passes over the snapshot share (analysis, orientation, holes, manifold, simplification, smoothing, self-intersections): the events of their spans, the device
 // counters and their pinned copy, all created by rc_pass_ready at the pass' first call and never before; `have`: a result of the current snapshot (of
-// the current analysis, for the orientation and the holes) exists.  rc_snapshot_changed / rc_analysis_changed below clear it.
+// the current analysis, for the orientation, the holes and the manifold pass) exists.  rc_snapshot_changed / rc_analysis_changed below clear it.
 struct RcPass {
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of up to three spans
     unsigned long long* h_cnt = nullptr;                       // pinned: the counters, and what the pass asks for behind them
@@ -232,6 +232,18 @@ struct RcHoles : RcPass {                                      // spans: holes, 
     RcBuf merged;                                              // the apply's faces ++ new_faces: it changes places with the caster's face buffer
     int64_t n_loops = 0;                                       // the tables' stride
     immesh_holes_stats st = {};
+};
+
+// one vertex per fan of faces (include/immesh_topology.h, the Manifold rule; topology/manifold_host.cpp): allocated at the first
+// immesh_topology_manifold, never before.  It reads the analysis' flag and sorted half-edges in RcTopology.
+struct RcManifold : RcPass {                                   // spans: manifold, apply; pinned [16] / [17]: the two words of n_fans
+    RcBuf parent, root, isroot, off, ncnt, nlnk, fanof;        // per corner (3 n_faces)
+    RcBuf key_a, key_b, val_a, val_b;                          // per fan: (vertex << 32) | root corner; _b sorted
+    RcBuf fv, head, scan, ft, vsrc;                            // per fan: its vertex, the run heads of the vertices and their scan, MT_TABLES int32 arrays
+    RcBuf start, nfans;                                        // per used vertex (and one more): its run of fans; per vertex: n_fans_out
+    RcBuf vtx_out, faces_out, fan_out;                         // the result: the apply makes the first two change places with the caster's buffers
+    int64_t n_fans = 0;                                        // the tables' stride
+    immesh_manifold_stats st = {};
 };
 
 // weld and vertex clustering of the snapshot (include/immesh_simplify.h; simplify/simplify_host.cpp): allocated at the first immesh_simplify, never
@@ -292,6 +304,7 @@ struct immesh_raycaster {
     RcTopology tp;
     RcOrient ot;
     RcHoles hl;
+    RcManifold mf;
     RcSimplify sp;
     RcSmooth so;
     RcIntersect ix;

@@ -178,13 +178,14 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
 }  // namespace
 
 // What a change of the caster's state discards.  A change of the snapshot is a build (rc_build: a rebuild, and the applies of a holes pass, a
-// simplification and a smoothing pass, which end in one) or the apply of an orientation, which keeps the hierarchy.  A new analysis replaces the old.
+// manifold pass, a simplification and a smoothing pass, which end in one) or the apply of an orientation, which keeps the hierarchy.  A new analysis replaces the old.
 //
 //   derived result                              | the snapshot changes  | a new analysis
 //   the last NEAREST cast, its reinforced points | discarded             | stay
 //   the samples (sm)                             | discarded             | stay
 //   the analysis (tp)                            | discarded             | replaced
-//   the orientation (ot), the holes pass (hl)    | discarded (they read the analysis) | discarded
+//   the orientation (ot), the holes pass (hl),   | discarded (they read the analysis) | discarded
+//   the manifold pass (mf)                       |
 //   the simplification's result (sp)             | discarded             | stays
 //   the smoothing pass' result (so)              | discarded             | stays
 //   the intersection pass' result (ix)           | discarded             | stays
@@ -196,6 +197,7 @@ int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, cons
 void rc_analysis_changed(immesh_raycaster* r) {
     r->ot.have = false;   // an orientation belongs to the analysis whose half-edges it read
     r->hl.have = false;   // and so does a holes pass
+    r->mf.have = false;   // and a manifold pass
 }
 
 void rc_snapshot_changed(immesh_raycaster* r) {

@@ -69,18 +69,10 @@ __global__ void __launch_bounds__(TP_BLOCK) ot_init_kernel(int64_t n_nodes, int3
     if (i < n_nodes) cover[i] = (int32_t)i;
 }
 
-// the head of a run of exactly two
-__device__ __forceinline__ bool ot_pair_head(const unsigned long long* __restrict__ key, int64_t i, int64_t n_half) {
-    if (i + 1 >= n_half) return false;
-    const unsigned long long k = key[i];
-    if (i > 0 && key[i - 1] == k) return false;
-    return key[i + 1] == k && !(i + 2 < n_half && key[i + 2] == k);
-}
-
 __global__ void __launch_bounds__(TP_BLOCK) ot_link_kernel(const unsigned long long* __restrict__ key, const int32_t* __restrict__ val, int64_t n_half,
                                                            const int32_t* __restrict__ faces, int32_t* cover, unsigned long long* cnt) {
     const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
-    if (i >= n_half || !ot_pair_head(key, i, n_half)) return;
+    if (i >= n_half || !tp_pair_head(key, i, n_half)) return;
     const int32_t h0 = val[i], h1 = val[i + 1];
     const int32_t f = h0 / 3, g = h1 / 3;                    // (two faces: a counting face uses three different edges)
     const int32_t d = tp_forward(faces, h0) == tp_forward(faces, h1) ? 1 : 0;
@@ -140,7 +132,7 @@ __global__ void __launch_bounds__(TP_BLOCK) ot_inconsistent_kernel(const unsigne
                                                                    int64_t n_bound) {
     const int64_t i = (int64_t)blockIdx.x * TP_BLOCK + threadIdx.x;
     int32_t c = -1;
-    if (i < n_half && ot_pair_head(key, i, n_half) && tp_forward(faces, val[i]) == tp_forward(faces, val[i + 1])) c = patch[val[i] / 3];
+    if (i < n_half && tp_pair_head(key, i, n_half) && tp_forward(faces, val[i]) == tp_forward(faces, val[i + 1])) c = patch[val[i] / 3];
     const bool p[1] = {c >= 0};
     int32_t* const t[1] = {tab + OT_NINCONSISTENT * n_bound};
     ot_fold<1>(c, p, t);

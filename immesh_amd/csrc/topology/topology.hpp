@@ -136,6 +136,41 @@ void hl_launch_decide(hipStream_t s, int64_t n_loops, int32_t* lt, unsigned long
 void hl_launch_emit(hipStream_t s, int64_t n_room, const int32_t* cycle, const int32_t* cloop, const int32_t* lt, int64_t n_loops, int32_t* new_faces,
                     int32_t* new_loop, unsigned long long* cnt);
 
+// manifold (manifold_kernels.hip) ---------------------------------------------------------------------------------------------------------
+// the manifold pass' device counters (int64 each; zeroed before every pass)
+enum {
+    MF_N_SINGULAR = 0, MF_MOST_FANS, MF_N_MOVED, MF_N_CHANGED, MF_N_CLOSED, MF_N_OPEN, MF_LARGEST_FAN, MF_ERROR, MF_COUNTERS = 16
+};
+// the per-fan tables: int32 arrays of n_fans entries each in one buffer, ft + k * n_fans: what immesh_topology_manifold_fans returns
+enum { MT_VERTEX = 0, MT_FIRST, MT_NCORNERS, MT_NLINKS, MT_INDEX, MT_TABLES };
+// parent[c] = c, ncnt[c] = nlnk[c] = 0 for the n3 = 3 n_faces corners
+void mf_launch_init(hipStream_t s, int64_t n3, int32_t* parent, int32_t* ncnt, int32_t* nlnk);
+// one lane per sorted half-edge: the head of a run of exactly two joins its users' corners at the edge's smaller vertex, and those at its larger
+// one.  cnt[MF_ERROR] != 0: a union ran out of its step bound.
+void mf_launch_link(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, int32_t* parent,
+                    unsigned long long* cnt);
+// root[c] = the root of corner c (-1: its face does not count), isroot[c], ncnt[root] += 1
+void mf_launch_flatten(hipStream_t s, const int32_t* parent, const int32_t* flag, int64_t n3, int32_t* root, int32_t* isroot, int32_t* ncnt);
+// the heads of runs of two again: nlnk[root] += 1 at either end
+void mf_launch_links(hipStream_t s, const unsigned long long* key, const int32_t* val, int64_t n_half, const int32_t* faces, const int32_t* root,
+                     int32_t* nlnk);
+// after the scan of isroot: key[off[c]] = (vertex << 32) | c and val[off[c]] = c for the roots (n_room entries of room)
+void mf_launch_keys(hipStream_t s, const int32_t* faces, const int32_t* isroot, const int32_t* off, int64_t n3, unsigned long long* key, int32_t* val,
+                    int64_t n_room);
+// sorted key j is fan j: fv[j] = its vertex, fanof[its root corner] = j
+void mf_launch_fans(hipStream_t s, const unsigned long long* key, int64_t n_fans, int64_t n3, int32_t* fv, int32_t* fanof);
+// after the run heads of fv and their scan: the tables; a fan that is no head is new vertex m = j - scan[j]: vsrc[m], and the three words of
+// its source in vtx_out[3 (n_vtx + m)] (n_new of room); cnt[MF_N_CLOSED], [MF_N_OPEN], [MF_LARGEST_FAN]
+void mf_launch_table(hipStream_t s, int64_t n_fans, const unsigned long long* key, const int32_t* head, const int32_t* scan, const int32_t* ncnt,
+                     const int32_t* nlnk, const float* vtx, int64_t n_vtx, int64_t n_new, int32_t* ft, int32_t* vsrc, float* vtx_out, unsigned long long* cnt);
+// one lane per run of fv (start: n_runs + 1 entries): nfans_out[vertex] = the run's length (zeroed by the caller); cnt[MF_N_SINGULAR], [MF_MOST_FANS]
+void mf_launch_vertices(hipStream_t s, int64_t n_runs, const int32_t* start, const int32_t* fv, int64_t n_fans, int64_t n_vtx, int32_t* nfans_out,
+                        unsigned long long* cnt);
+// faces_out[3 f + k] = the output index of the corner's fan, fan_out[3 f + k] its number; a face that does not count is copied, with -1;
+// cnt[MF_N_MOVED], [MF_N_CHANGED]
+void mf_launch_emit(hipStream_t s, const int32_t* faces, int64_t n_faces, const int32_t* flag, const int32_t* root, const int32_t* fanof, const int32_t* ft,
+                    int64_t n_fans, int32_t* faces_out, int32_t* fan_out, unsigned long long* cnt);
+
 // select ----------------------------------------------------------------------------------------------------------------------------------
 // rank_key[c] = ((2^31 - 1 - nfaces[c]) << 32) | c, iota[c] = c
 void tp_launch_rank_keys(hipStream_t s, const int32_t* nfaces, int64_t n_comp, unsigned long long* rank_key, int32_t* iota);

@@ -58,4 +58,12 @@ __device__ __forceinline__ bool tp_forward(const int32_t* __restrict__ faces, in
     return faces[3 * f + k] < faces[3 * f + (k == 2 ? 0 : k + 1)];
 }
 
+// sorted half-edge i is the head of a run of exactly two: an edge with two uses, whose users are val[i] / 3 and val[i + 1] / 3
+__device__ __forceinline__ bool tp_pair_head(const unsigned long long* __restrict__ key, int64_t i, int64_t n_half) {
+    if (i + 1 >= n_half) return false;
+    const unsigned long long k = key[i];
+    if (i > 0 && key[i - 1] == k) return false;
+    return key[i + 1] == k && !(i + 2 < n_half && key[i + 2] == k);
+}
+
 }  // namespace

@@ -1,6 +1,6 @@
 /* immesh_topology.h -- the topology of a built ray caster's snapshot on the device: connected components, open edges, non-manifold and
- * inconsistently wound edges, boundary loops, the Euler characteristic, a filter that drops small fragments, one winding per manifold patch, and
- * the boundary cycles in order with a fill of the small holes (libimmesh_hip.so).
+ * inconsistently wound edges, boundary loops, the Euler characteristic, a filter that drops small fragments, one winding per manifold patch, the
+ * boundary cycles in order with a fill of the small holes, and a split of every pinched vertex and fin (libimmesh_hip.so).
  *
  * Reference: none.  The reference writes its mesh to a PLY and leaves "remove isolated pieces" to a desktop tool; nothing pins this module but the
  * contract below and its checker (tests/topology_checker.py: np.unique on the edge keys, a plain union-find loop).
@@ -127,6 +127,42 @@
  * 0 <= max_diagonal finite; cap >= 0; a holes pass of the current analysis before any fetch or apply; for the apply n_faces + n_new <= 2^30 and
  * 3 (n_faces + n_new) <= 2^31 - 2, so that the result can be analysed -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the
  * caster, a new analysis or an orient-apply discards the holes pass.  Zero loops give all zeros; that is not an error.
+ *
+ * ---- Manifold (exact: integers, and bit copies of floats; as order-free as the above) -----------------------------------------------------------
+ * immesh_topology_manifold gives every fan of faces round a vertex a vertex of its own: the step a desktop tool calls "split non-manifold
+ * vertices".  It reads the analysis of the current snapshot; nothing reaches the caster before _apply.  The rules about counting faces, edges and
+ * uses above apply unchanged.
+ *   Corner:  corner 3 f + k is vertex i_k of counting face f.  A face that does not count has no corners.
+ *   Link:    two corners at the same vertex v, in faces f and g, are linked when f and g are the two users of an edge with uses == 2 that has v as
+ *            an endpoint.  The direction of the uses plays no part: the rule works on an unoriented mesh.  Edges with one use, or with three and
+ *            more, link nothing (the patch rule of the Orientation).
+ *   Fan:     the fans are the classes of the transitive closure of the links among the corners of one vertex.  A fan's LABEL is the smallest face
+ *            index among its corners; n_corners is the number of its faces; n_links the number of linking edges between two of its corners.  A fan
+ *            is CLOSED when n_links == n_corners, else OPEN.  Fans are numbered 0 .. n_fans - 1 by ascending (vertex, label).
+ *   Output index: the fan of v with the smallest label keeps index v.  Every other fan gets a new index n_vtx + j, j counting the new vertices in
+ *            fan order; vsrc[j] is the source vertex, and new vertex j is a bit copy of the three floats of vsrc[j], NaN payloads and the sign of a
+ *            zero included.  vtx_out = vtx ++ the copies.  Unused vertices stay where they are.
+ *   Faces:   faces_out holds all n_faces faces in face order, each corner replaced by its fan's output index; the faces that do not count are
+ *            copied.  fan_out[3 f + k] is the fan number of the corner, or -1.
+ *   Per vertex: n_fans_out[v] = the number of fans at v, 0 for an unused vertex.  A vertex is SINGULAR when it has 2 or more fans.
+ *   Stats:   n_corners (3 n_counting), n_fans, n_vertices_used, n_singular_vertices, most_fans_at_vertex, n_new_vertices (n_fans -
+ *            n_vertices_used), n_corners_moved (corners whose index changes), n_faces_changed (faces with such a corner), n_closed_fans,
+ *            n_open_fans, largest_fan_corners, n_nonmanifold_before (the analysis' count).
+ *   Guarantee: the output has no non-manifold edge and no singular vertex, for any input.  An output edge {a, b} is used by exactly the original
+ *            users of {u, w} whose corners lie in fan a at u and in fan b at w.  Within a fan each corner has at most two links, one per edge of
+ *            its face at the vertex, and a connected graph of degree at most 2 is a path or a cycle.  A corner whose face uses an edge {u, w} that
+ *            is not interior has lost the link across that edge, so it is an end of a path, and a path has two ends: at most two users of any
+ *            original edge share a fan at u, hence an output edge.  Original links survive as output edges with two uses (both ends of a linking
+ *            edge keep their two users together), so the corners of an output vertex are still one class: every used output vertex has one fan.
+ *   Invariant: an analysis of (vtx_out, faces_out) has n_nonmanifold == 0; n_counting and n_degenerate unchanged; n_vertices_used == n_fans;
+ *            n_boundary + 2 n_interior == 3 n_counting; n_interior and n_components not smaller.  A second pass on that output has
+ *            n_new_vertices == 0 and faces_out equal to its input.  When every patch of the output is orientable and its orientation is applied,
+ *            every boundary loop is simple.
+ *   Apply:   afterwards the caster behaves in every call as one freshly built by immesh_raycast_build_triangles from vtx_out and faces_out: equal
+ *            answers bit for bit, and everything a build discards is discarded.  No host round trip of the mesh.
+ * Validated before any launch: an analysis of the current snapshot; cap >= 0; a manifold pass of the current analysis before any fetch or apply;
+ * for the apply n_vtx + n_new_vertices <= 2^31 - 1 -- else IMMESH_E_INVAL with text in immesh_last_error(ctx).  A rebuild of the caster, a new
+ * analysis or any apply discards the result.  Zero faces give all zeros; that is not an error.  IMMESH_E_INTERNAL as above; the pass is void.
  */
 #ifndef IMMESH_TOPOLOGY_H
 #define IMMESH_TOPOLOGY_H
@@ -249,6 +285,42 @@ int immesh_topology_holes_apply(immesh_raycaster* rc);
 /* Device time in milliseconds from HIP events on the caster's stream: [0] the last holes pass (every launch)  [1] the last apply (the copies and the
  * build of the hierarchy). */
 int immesh_topology_holes_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] holes  [1] apply */
+
+typedef struct immesh_manifold_stats {
+    int64_t n_corners;                /* 3 n_counting */
+    int64_t n_fans;
+    int64_t n_vertices_used;
+    int64_t n_singular_vertices;
+    int64_t most_fans_at_vertex;
+    int64_t n_new_vertices;           /* n_fans - n_vertices_used */
+    int64_t n_corners_moved;
+    int64_t n_faces_changed;
+    int64_t n_closed_fans;
+    int64_t n_open_fans;
+    int64_t largest_fan_corners;
+    int64_t n_nonmanifold_before;     /* the analysis' n_nonmanifold */
+} immesh_manifold_stats;
+
+/* The Manifold rule on the analysed snapshot; stats may be NULL.  Nothing is allocated or launched for the pass before the first call; the buffers
+ * are grow-only.  The result stays on the device for the calls below until the caster is rebuilt, analysed again, or any apply has run.  One
+ * read-back lies between its launches: the number of fans, which sizes the sort of their keys. */
+int immesh_topology_manifold(immesh_raycaster* rc, immesh_manifold_stats* stats);
+/* n_fans_out[v], n_vtx int32. */
+int immesh_topology_manifold_vertices(immesh_raycaster* rc, int32_t* n_fans_out /* n_vtx */);
+/* The fan tables, n_fans entries each.  Every pointer may be NULL; n_out gets n_fans.  With any array given, cap < n_fans is IMMESH_E_CAPACITY
+ * (n_out is still set). */
+int immesh_topology_manifold_fans(immesh_raycaster* rc, int32_t* vertex, int32_t* first_face, int32_t* n_corners, int32_t* n_links, int32_t* index_out,
+                                  int64_t cap, int64_t* n_out);
+/* fan_out and faces_out, 3 n_faces int32 each; each may be NULL. */
+int immesh_topology_manifold_faces(immesh_raycaster* rc, int32_t* fan_out, int32_t* faces_out);
+/* The new vertices: vsrc n_new_vertices int32, xyz 3 floats per new vertex; each may be NULL; n_out gets n_new_vertices.  With an array given,
+ * cap < n_new_vertices is IMMESH_E_CAPACITY. */
+int immesh_topology_manifold_new_vertices(immesh_raycaster* rc, int32_t* vsrc, float* xyz, int64_t cap, int64_t* n_out);
+/* The Apply rule: vtx_out and faces_out change places with the caster's buffers, then the caster's own build; no host round trip of the mesh. */
+int immesh_topology_manifold_apply(immesh_raycaster* rc);
+/* Device time in milliseconds from HIP events on the caster's stream: [0] the last manifold pass (every launch, and the one read-back of the number
+ * of fans between them)  [1] the last apply (the build of the hierarchy). */
+int immesh_topology_manifold_last_timing(immesh_raycaster* rc, float ms[2]);   /* [0] manifold  [1] apply */
 
 #ifdef __cplusplus
 }

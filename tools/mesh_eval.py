@@ -36,6 +36,11 @@ include/immesh_intersect.h), all off by default:
                             (immesh_self_intersect) and take every face of such a pair out on the device (immesh_self_intersect_apply); the fragment
                             filter, the orientation and --fill-holes then see the holes it left.  The output gains an `intersections_removed` block:
                             the pass' counts and the faces that went.  Weld first: the neighbours of an unwelded soup touch and count
+  --manifold                after --weld / --simplify and --remove-self-intersections, before the fragment filter, the orientation and --fill-holes:
+                            give every fan of faces round a vertex a vertex of its own (immesh_topology_analyse, immesh_topology_manifold,
+                            immesh_topology_manifold_apply, and an analysis of the result): pinched vertices and fins come apart, no edge keeps three
+                            uses, and the holes that touched in a vertex become simple loops that --fill-holes can close.  The output gains a
+                            `manifold` block: the pass' counts, and n_nonmanifold_after, n_components_after and n_boundary_loops_after
   --self-intersections [--max-candidates N]
                             the self-intersection counts of the mesh that is evaluated, after every other clean-up option, in an `intersections`
                             block.  N bounds the candidate pairs of either option (2^24 by default): a mesh with more is refused
@@ -53,7 +58,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--fill-holes MAX_EDGES [--fill-max-diagonal D]]
                               [--weld | --simplify CELL [--simplify-mode first|mean]] [--keep-duplicate-faces]
                               [--smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]]
-                              [--remove-self-intersections] [--self-intersections] [--max-candidates N]
+                              [--remove-self-intersections] [--self-intersections] [--max-candidates N] [--manifold]
                               [--align point|plane [--align-max-dist D] [--align-iters N]]
 """
 import argparse
@@ -149,6 +154,19 @@ def fill_holes(h, max_edges, max_diagonal=0.0):
     return h._raycast_sizes(), {"max_edges": max_edges, "max_diagonal": max_diagonal, **{n: getattr(st, n) for n, _ in capi.HolesStats._fields_}}
 
 
+def manifold(h, vtx):
+    """h: a HotPath whose caster is built over the vertices vtx -> every fan of faces gets a vertex of its own on the device (analyse, manifold, apply, analyse again);
+    returns (the caster's sizes, the new vertices and faces as the later steps need them on the host, the counts)"""
+    h.topology_analyse()
+    st = h.topology_manifold()
+    vtx = np.concatenate([np.asarray(vtx, np.float32).reshape(-1, 3), h.topology_manifold_new_vertices()[1]])
+    faces = h.topology_manifold_faces()[1]
+    h.topology_manifold_apply()
+    after = h.topology_analyse()
+    return h._raycast_sizes(), vtx, faces, {**{n: getattr(st, n) for n, _ in capi.ManifoldStats._fields_}, "n_nonmanifold_after": after.n_nonmanifold,
+                                            "n_components_after": after.n_components, "n_boundary_loops_after": after.n_boundary_loops}
+
+
 SIMPLIFY_MODES = {"first": capi.SIMPLIFY_FIRST, "mean": capi.SIMPLIFY_MEAN}
 
 
@@ -238,6 +256,7 @@ def main():
     ap.add_argument("--remove-self-intersections", action="store_true", help="take the faces that pass through each other out, right after --weld / --simplify")
     ap.add_argument("--self-intersections", action="store_true", help="add the evaluated mesh's self-intersection counts to the output")
     ap.add_argument("--max-candidates", type=int, default=None, metavar="N", help="with either of the two: refuse a mesh with more candidate pairs (2^24)")
+    ap.add_argument("--manifold", action="store_true", help="split every pinched vertex and fin: a vertex per fan of faces, before the orientation and --fill-holes")
     ap.add_argument("--align", choices=sorted(ALIGN_MODES), default=None, help="refine the cloud's pose against the evaluated mesh first (ICP with point or plane rows)")
     ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="with --align: pairs farther apart do not take part (1.0)")
     ap.add_argument("--align-iters", type=int, default=None, metavar="N", help="with --align: at most N iterations (30)")
@@ -269,6 +288,8 @@ def main():
             sizes, vtx, faces, extra["simplify"] = simplify(h, 0.0 if args.weld else args.simplify, args.simplify_mode, not args.keep_duplicate_faces)
         if args.remove_self_intersections:
             sizes, faces, extra["intersections_removed"] = remove_self_intersections(h, faces, max_candidates)
+        if args.manifold:
+            sizes, vtx, faces, extra["manifold"] = manifold(h, vtx)
         if args.min_component_faces > 0:
             sizes, extra["filter"] = drop_fragments(h, vtx, faces, args.min_component_faces)
         if args.orient:
