@@ -221,6 +221,7 @@ static int run_residual_pass(immesh_ctx* c, const float* d_pts, int n, const imh
     const double ticket = (double)(++c->res_ticket);
     RegIterArgs& a = c->reg_args;
     a.mode = REG_MODE_HOST; a.it = 0; a.max_iter = c->cfg.max_iter; a.sp = sp;
+    a.pad = c->knobs.match_seq ? 4 : 0;   // (not what the context's last registration left there: launch_residual picks the matcher by this bit)
     launch_residual(c->stream, c->map, a, c->d_regstate, d_pts, n, c->d_partials, c->d_done, c->d_out48_host, c->d_reg_out_host, ticket, c->d_match, c->d_mnode, c->d_dis,
                     c->d_rinv, c->d_normal);
     volatile double* flag = c->h_out48 + RES_TICKET;
@@ -287,11 +288,11 @@ static int register_enqueue_fused(immesh_ctx* c, const float* d_pts, int n_ds, c
     std::memcpy(a.prior, prior.R, 72); std::memcpy(a.prior + 9, prior.t, 24); std::memcpy(a.prior + 12, prior.vel, 24); std::memcpy(a.prior + 15, prior.bg, 24);
     std::memcpy(a.prior + 18, prior.ba, 24); std::memcpy(a.prior + 21, prior.g, 24);
     c->reg_ticket = (double)(++c->res_ticket);
+    if (c->knobs.match_seq) a.pad |= 4;            // (every route: launch_residual and launch_residual_persistent pick the matcher by this bit)
     if (!c->rccl_comm) {
         // ONE launch for the scan: a resident grid runs every pass and the 18-state update (residual_persistent_kernel); a.mat = the prior covariance
         a.mode = REG_MODE_FUSED; a.it = 0;
         if (c->knobs.rp_force_abort) a.pad |= 2;   // (IMMESH_RP_FORCE_ABORT: the test hook of the bounded gather)
-        if (c->knobs.match_seq) a.pad |= 4;
         std::memcpy(a.mat, st.cov, sizeof(a.mat));
         const int par = (c->rp_parity ^= 1);   // this scan's slot buffer; the launch re-arms the other one for the next scan
         RpEpilogue none{};
@@ -328,7 +329,7 @@ static int register_collect_fused(immesh_ctx* c, int n_ds, imh::State& st, int* 
 static int register_fallback_chain(immesh_ctx* c, const float* d_pts, int n_ds, const imh::State& st) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->rp_fallbacks++;
-    c->reg_args.pad = 0;
+    c->reg_args.pad = c->knobs.match_seq ? 4 : 0;
     c->reg_ticket = (double)(++c->res_ticket);
     return register_enqueue_chain(c, d_pts, n_ds, st);
 }
