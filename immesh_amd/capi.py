@@ -1070,6 +1070,97 @@ class HotPath:
         self._check(f(self.cloud_index(), ms), "nearest_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    # -- k nearest neighbours, radius counts, outlier removal on the cloud index (include/immesh_nearest.h) -------------------------------------------
+    def _cloud_index_given(self):
+        g = self.lib.immesh_cloud_index_sizes; g.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; g.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(g(self.cloud_index(), C.byref(n), None), "cloud_index_sizes")
+        return n.value
+
+    def _knn_outputs(self, n, k, want):
+        kk = max(int(k), 0) if int(k) <= 64 else 0                                   # (a bad k is the library's to reject)
+        out = {"count": np.empty(n, np.int32), "index": np.empty((n, kk), np.int32), "d2": np.empty((n, kk), np.float64), "mean": np.empty(n, np.float64)}
+        return {key: v for key, v in out.items() if key in want}
+
+    def knn_points(self, pts, k, max_dist, frame=None, want=("count", "index", "d2")):
+        """immesh_knn_points: pts (n, 3) in the world (frame None) or in the sensor frame -> dict of the wanted outputs: count (n,) int32,
+        index (n, k) int32 and d2 (n, k) float64, ascending in (d2, index), -1 in the slots past count"""
+        f = self.lib.immesh_knn_points
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 3; f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        out = self._knn_outputs(len(p), k, [w for w in want if w != "mean"])
+        self._check(f(self.cloud_index(), None if frame is None else C.byref(frame), _ptr(p), len(p), k, max_dist,
+                      *[_ptr(out.get(key)) for key in ("count", "index", "d2")]), "knn_points")
+        return out
+
+    def knn_cloud(self, k, max_dist, want=("count", "index", "d2", "mean")):
+        """immesh_knn_cloud: every point of the index's cloud against the others -> the dict of knn_points and mean (n,) float64 (-1: no neighbour);
+        without index and d2 the lists are not stored on the device"""
+        f = self.lib.immesh_knn_cloud; f.argtypes = [C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 4; f.restype = C.c_int
+        out = self._knn_outputs(self._cloud_index_given(), k, want)
+        self._check(f(self.cloud_index(), k, max_dist, *[_ptr(out.get(key)) for key in ("count", "index", "d2", "mean")]), "knn_cloud")
+        return out
+
+    def radius_count_points(self, pts, radius, frame=None):
+        """immesh_radius_count_points -> (n,) int32: the cloud points within radius of every query"""
+        f = self.lib.immesh_radius_count_points
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.c_double, C.c_void_p]; f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        count = np.empty(len(p), np.int32)
+        self._check(f(self.cloud_index(), None if frame is None else C.byref(frame), _ptr(p), len(p), radius, _ptr(count)), "radius_count_points")
+        return count
+
+    def radius_count_cloud(self, radius):
+        """immesh_radius_count_cloud -> (n,) int32: the other cloud points within radius of every cloud point"""
+        f = self.lib.immesh_radius_count_cloud; f.argtypes = [C.c_void_p, C.c_double, C.c_void_p]; f.restype = C.c_int
+        count = np.empty(self._cloud_index_given(), np.int32)
+        self._check(f(self.cloud_index(), radius, _ptr(count)), "radius_count_cloud")
+        return count
+
+    @staticmethod
+    def _outlier_counts(counts):
+        return dict(zip(("kept", "outliers", "isolated", "not_finite"), (int(v) for v in counts)))
+
+    def cloud_outliers_statistical(self, mult):
+        """immesh_cloud_outliers_statistical over the last knn_cloud -> dict: mu, sigma, threshold, kept, outliers, isolated, not_finite, keep (n,) bool"""
+        f = self.lib.immesh_cloud_outliers_statistical; f.argtypes = [C.c_void_p, C.c_double] + [C.c_void_p] * 5; f.restype = C.c_int
+        mu, sigma, thr = C.c_double(0), C.c_double(0), C.c_double(0)
+        counts = np.zeros(4, np.int64)
+        keep = np.zeros(self._cloud_index_given(), np.uint8)
+        self._check(f(self.cloud_index(), mult, C.byref(mu), C.byref(sigma), C.byref(thr), _ptr(counts), _ptr(keep)), "cloud_outliers_statistical")
+        return dict(mu=mu.value, sigma=sigma.value, threshold=thr.value, keep=keep.astype(bool), **self._outlier_counts(counts))
+
+    def cloud_outliers_radius(self, min_neighbours):
+        """immesh_cloud_outliers_radius over the last radius_count_cloud -> dict: kept, outliers, isolated, not_finite, keep (n,) bool"""
+        f = self.lib.immesh_cloud_outliers_radius; f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        counts = np.zeros(4, np.int64)
+        keep = np.zeros(self._cloud_index_given(), np.uint8)
+        self._check(f(self.cloud_index(), min_neighbours, _ptr(counts), _ptr(keep)), "cloud_outliers_radius")
+        return dict(keep=keep.astype(bool), **self._outlier_counts(counts))
+
+    def cloud_index_apply_outliers(self):
+        """immesh_cloud_index_apply_outliers: the kept points of the last mask become the index's cloud -> their old indices (n_kept,) int32"""
+        f = self.lib.immesh_cloud_index_apply_outliers; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        kept = np.empty(self._cloud_index_given(), np.int32)                          # at most every point is kept
+        n = C.c_int64(0)
+        self._check(f(self.cloud_index(), _ptr(kept), len(kept), C.byref(n)), "cloud_index_apply_outliers")
+        return kept[:n.value].copy()
+
+    def cloud_index_points(self):
+        """immesh_cloud_index_points: the index's cloud as it lies on the device -> (n, 3) float32"""
+        f = self.lib.immesh_cloud_index_points; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        xyz = np.empty((self._cloud_index_given(), 3), np.float32)
+        n = C.c_int64(0)
+        self._check(f(self.cloud_index(), _ptr(xyz), len(xyz), C.byref(n)), "cloud_index_points")
+        return xyz
+
+    def knn_timing(self):
+        """device milliseconds of the last (traversal of a neighbours / count query, mask, apply)"""
+        f = self.lib.immesh_knn_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.cloud_index(), ms), "knn_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     # -- the topology of the caster's snapshot (include/immesh_topology.h) ----------------------------------------------------------------------------
     def topology_analyse(self):
         """immesh_topology_analyse on the caster's snapshot -> TopologyStats; the analysis stays on the device for the calls below"""

@@ -3,7 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <utility>
-#include "../../../include/immesh_closest.h"     // (and immesh_raycast.h): the frame and the distance statistics
+#include <vector>
+#include "../../../include/immesh_closest.h"    // (and immesh_raycast.h): the frame and the distance statistics
 #include "../../../include/immesh_topology.h"    // the stats the passes' records hold
 #include "../../../include/immesh_simplify.h"
 #include "../../../include/immesh_smooth.h"
@@ -340,6 +341,29 @@ void dq_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, in
                      unsigned long long* hist, DqStatsDev* res);
 
 // ---- mesh-to-cloud distances (include/immesh_nearest.h): nearest_host.cpp owns the index and the sampler's host side ---------------------------------
+// k nearest neighbours, radius counts, the outlier masks and their apply on a cloud index (knn_host.cpp): allocated at the first call of one of
+// them, never before.  A build and an apply clear the three flags.
+struct RcKnn {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // traversal, mask, apply: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the mask's four counts
+    RcBuf pts;                                                 // the last point-mode query's points
+    RcBuf cnt, idx, d2;                                        // the last Neighbours query of either mode: counts, and the lists when asked for
+    RcBuf mean, status;                                        // the last cloud-mode Neighbours query (the statistical rule reads them)
+    RcBuf rcnt, rstatus;                                       // the last cloud-mode Count query (the radius rule reads them)
+    RcBuf pstatus;                                             // a point-mode query's status (nothing reads it afterwards)
+    RcBuf flag, keep8, off, mcnt;                              // the last mask as int32 and uint8, its scan, its four device counts
+    RcBuf out, kept;                                           // the apply: out changes places with the index's cloud; kept: the old indices
+    std::vector<double> h_mean;                                // the statistical rule's one read-back
+    bool have_knn = false, have_count = false, have_mask = false;
+    int64_t n_kept = 0;
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    void changed() { have_knn = have_count = have_mask = false; }
+    ~RcKnn() {
+        rc_destroy_events(ev, 6);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi, built by the same rc_tree_build, one point per leaf.
 struct immesh_cloud_index {
     immesh_ctx* ctx = nullptr;
@@ -353,6 +377,7 @@ struct immesh_cloud_index {
     bool built = false;
     int64_t n_pts = 0;
     float ms[3] = {0.0f, 0.0f, 0.0f};
+    RcKnn kn;
 };
 
 // nearest cloud point of every query; status[i] as rc_launch_closest writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
@@ -365,3 +390,19 @@ void ms_launch_count(hipStream_t s, const float* vtx, int64_t n_vtx, const int32
 // sample s of n_samples (the total, below 2^31 - 1): sample s - off[f] of the face f it falls into by the offsets
 void ms_launch_emit(hipStream_t s, const float* vtx, const int32_t* faces, int64_t n_faces, uint64_t seed, const int32_t* off, int64_t n_samples, float* xyz,
                     int32_t* face);
+
+// ---- k nearest neighbours, radius counts, outlier masks and their apply (include/immesh_nearest.h, the Neighbours / Count / Outliers rules): knn_host.cpp
+// the transfer lists of the last k-nearest query, n x k entries (not grown, and not written, when neither list is asked for)
+// status[i]: 0 candidates, 1 finite but none within the distance, 2 the query is not finite.  mode 0: pts are world floats, 1: pts through fr,
+// 2: cloud mode (query i is cloud point i, and index i is no candidate).  index / d2 may both be NULL (no list is stored); mean only in mode 2.
+void kn_launch_knn(hipStream_t s, const RcFrame& fr, int mode, const float* pts, int64_t n, int32_t k, double r2, const float* cloud, const RcNode* nodes,
+                   int64_t n_in, int32_t* count, int32_t* index, double* d2, double* mean, uint8_t* status);
+void kn_launch_count(hipStream_t s, const RcFrame& fr, int mode, const float* pts, int64_t n, double r2, const float* cloud, const RcNode* nodes, int64_t n_in,
+                     int32_t* count, uint8_t* status);
+// the masks: flag[i] (int32, what the scan reads) = keep8[i] = keep_i; cnt[0 .. 3] (zeroed by the caller) += kept, outliers, isolated, not finite
+void kn_launch_mask_statistical(hipStream_t s, const double* mean, const uint8_t* status, int64_t n, double threshold, int32_t* flag, uint8_t* keep8,
+                                unsigned long long* cnt);
+void kn_launch_mask_radius(hipStream_t s, const int32_t* count, const uint8_t* status, int64_t n, int32_t min_neighbours, int32_t* flag, uint8_t* keep8,
+                           unsigned long long* cnt);
+// the apply's compaction behind the exclusive scan of flag: out[off[i]] = pts[i], kept[off[i]] = i for the kept points (off[i] checked against n_kept)
+void kn_launch_compact(hipStream_t s, const float* pts, const int32_t* flag, const int32_t* off, int64_t n, int64_t n_kept, float* out, int32_t* kept);

@@ -141,4 +141,43 @@ __device__ __forceinline__ void dq_walk(const RcNode* __restrict__ nodes, const 
     }
 }
 
+// dq_walk's sibling for queries that keep more than one leaf (k nearest, radius count): the same order, the same pruning rule !(L > bound) and the
+// same float keys rounded down, but the leaf is *offered* -- sink.offer(id) takes it or not and returns the bound that holds from then on (r2 until a
+// k-list is full, then its k-th D; r2 throughout for a count).  The bound never grows.  A node with L == bound is still entered: it can hold a point
+// at the k-th D with a lower index.  The single-leaf tree names its one leaf as both children (rc_launch_single); a list
+// would hold it twice and a counter count it twice, so n_in == 1 is offered once, by rule, and no node is read.
+template <class Sink>
+__device__ __forceinline__ void dq_walk_offer(const RcNode* __restrict__ nodes, int64_t n_in, const double* p, double bound, Sink& sink) {
+    if (n_in == 1) { (void)sink.offer(~nodes[0].child[0]); return; }
+    int32_t stack[RC_STACK];
+    float stack_key[RC_STACK];
+    int sp = 0;
+    int32_t cur = 0;
+    for (;;) {
+        if (cur < 0) {   // a leaf
+            bound = sink.offer(~cur);
+        } else {
+            const RcNode& nd = nodes[cur];
+            const double l0 = dq_box(p, nd.lo[0], nd.hi[0]), l1 = dq_box(p, nd.lo[1], nd.hi[1]);
+            const bool h0 = !(l0 > bound), h1 = !(l1 > bound);
+            const int32_t c0 = nd.child[0], c1 = nd.child[1];
+            if (h0 && h1) {
+                const bool first0 = l0 <= l1;
+                stack[sp] = first0 ? c1 : c0;
+                stack_key[sp] = dq_round_down(first0 ? l1 : l0);
+                sp++;
+                cur = first0 ? c0 : c1;
+                continue;
+            }
+            if (h0 || h1) { cur = h0 ? c0 : c1; continue; }
+        }
+        bool found = false;
+        while (sp > 0) {
+            sp--;
+            if (!((double)stack_key[sp] > bound)) { cur = stack[sp]; found = true; break; }
+        }
+        if (!found) break;
+    }
+}
+
 }  // namespace

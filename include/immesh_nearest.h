@@ -47,6 +47,35 @@
  * the caster and the index of one context; 0 < bin_width finite, 1 <= n_bins <= 2^20, a query before the reduction; else IMMESH_E_INVAL with text in
  * immesh_last_error(ctx).  An empty index (no point, or none that is finite) answers "no neighbour" for every query, and a caster with no face
  * gives zero samples; neither is an error.
+ *
+ * ---- The Neighbours rule, the Count rule, the Outliers rule (the same arithmetic; the Point, Cloud, D and Box rules above stay as they stand) ------
+ *   Candidates: for a query p, the cloud points in the index with D <= r2 (r2 = max_dist max_dist, or radius radius).  In cloud mode the query is
+ *            cloud point i itself, read where it lies on the device (its floats widened, no frame), and the point with index i is no candidate;
+ *            another point with equal coordinates is one, at D = 0.  A cloud point that is not finite is a query "not finite" without candidates.
+ *   Neighbours: 1 <= k <= 64.  The result is the first min(k, #candidates) candidates in ascending (D, index) order, in that order.
+ *            count_out[i] (int32) their number; index_out[i k + j] (int32) and d2_out[i k + j] (double) the j-th; slots j >= count hold -1 and -1.0.
+ *            Cloud mode: mean_out[i] = (the sum over j, in list order, of sqrt(d2_j)) / (double)count, a sequential sum of correctly rounded double
+ *            square roots; -1.0 when count == 0.  Every output may be NULL; with both lists NULL the n x k lists are not stored on the device at all.
+ *   Count:   count_out[i] (int32) = the number of candidates.
+ *   Outliers, statistical (over the index's last cloud-mode Neighbours query): used = the cloud points with count > 0, n_used their number;
+ *            mu = (the sequential double sum of mean_i over used, ascending i) / (double)n_used;
+ *            sigma = sqrt((the sequential sum of (mean_i - mu) (mean_i - mu) over used, ascending i) / (double)(n_used - 1)), 0 when n_used <= 1;
+ *            threshold = mu + mult sigma;  keep_i = used_i && mean_i <= threshold.  mu and sigma are host code over the mean array read back once;
+ *            the mask is made on the device from the threshold.  n_used == 0: mu = sigma = threshold = 0, nothing is kept, and that is no error.
+ *            counts: [0] kept  [1] statistical outliers (used, above the threshold)  [2] isolated (finite, count == 0)  [3] not finite; they sum to
+ *            the cloud's size.
+ *   Outliers, radius (over the index's last cloud-mode Count query): keep_i = finite_i && count_i >= min_neighbours, min_neighbours >= 0.
+ *            counts: [0] kept  [1] finite and not kept  [2] isolated (finite, count == 0: kept when min_neighbours == 0, else among [1])
+ *            [3] not finite; [0] + [1] + [3] is the cloud's size.
+ *            keep_out (either rule) is one uint8 per cloud point, 1 for a kept point.
+ *   Apply:   the kept points of the index's last mask, in ascending old index, become the index's cloud (a scan of the mask, a compaction and the
+ *            build, all on the device).  kept_index_out receives the old index of every new point: cap < their number with kept_index_out given is
+ *            IMMESH_E_CAPACITY, and the index stays as it was.  Earlier query results and masks of the index are dropped: a reduction afterwards is
+ *            IMMESH_E_INVAL, and so is an Outliers call before a new cloud-mode query.  An index left empty answers "no neighbour" and is no error.
+ * These results, too, are functions of the cloud, the queries and the parameters alone.
+ * Validated before any launch: a built index; 1 <= k <= 64; 0 < max_dist and 0 < radius, finite; mult finite and >= 0; min_neighbours in
+ * [0, 2^31 - 2]; the matching cloud-mode query made since the last build or apply before an Outliers call; a mask before the apply; the point array
+ * and the frame as above; else IMMESH_E_INVAL with text, and the index stays as it was.
  */
 #ifndef IMMESH_NEAREST_H
 #define IMMESH_NEAREST_H
@@ -92,6 +121,30 @@ int immesh_nearest_last_timing(immesh_cloud_index* ix, float ms[3]);
 /* Device time in milliseconds of the caster's last immesh_mesh_sample (HIP events on the caster's stream): [0] the counts  [1] the scan and the emit
  * launch.  The read-back of the total lies between the two and is not included. */
 int immesh_mesh_sample_last_timing(immesh_raycaster* rc, float ms[2]);
+
+/* The Neighbours rule for n points (n x 3 floats, host memory; frame as for immesh_nearest_points): count_out n int32, index_out n x k int32,
+ * d2_out n x k doubles; each may be NULL. */
+int immesh_knn_points(immesh_cloud_index* ix, const immesh_ray_frame* frame, const float* pts, int64_t n, int32_t k, double max_dist, int32_t* count_out,
+                      int32_t* index_out, double* d2_out);
+/* The same in cloud mode: every point of the index's cloud against the others; the outputs are sized by the cloud (immesh_cloud_index_sizes, points
+ * given); mean_out one double per point.  The means and the counts stay on the device for immesh_cloud_outliers_statistical. */
+int immesh_knn_cloud(immesh_cloud_index* ix, int32_t k, double max_dist, int32_t* count_out, int32_t* index_out, double* d2_out, double* mean_out);
+/* The Count rule for n points, and in cloud mode (the counts stay on the device for immesh_cloud_outliers_radius). */
+int immesh_radius_count_points(immesh_cloud_index* ix, const immesh_ray_frame* frame, const float* pts, int64_t n, double radius, int32_t* count_out);
+int immesh_radius_count_cloud(immesh_cloud_index* ix, double radius, int32_t* count_out);
+/* The Outliers rules: the mask of the cloud on the device, for immesh_cloud_index_apply_outliers.  mu, sigma, threshold, counts (four int64) and
+ * keep_out (one uint8 per cloud point) may each be NULL. */
+int immesh_cloud_outliers_statistical(immesh_cloud_index* ix, double mult, double* mu, double* sigma, double* threshold, int64_t counts[4],
+                                      uint8_t* keep_out);
+int immesh_cloud_outliers_radius(immesh_cloud_index* ix, int64_t min_neighbours, int64_t counts[4], uint8_t* keep_out);
+/* The Apply rule.  n_out (may be NULL) receives the number of kept points; kept_index_out (that many int32) may be NULL. */
+int immesh_cloud_index_apply_outliers(immesh_cloud_index* ix, int32_t* kept_index_out, int64_t cap, int64_t* n_out);
+/* The index's cloud as it lies on the device (points given x 3 floats, points that are not finite included); cap < that count with xyz_out given is
+ * IMMESH_E_CAPACITY.  n_out may be NULL. */
+int immesh_cloud_index_points(immesh_cloud_index* ix, float* xyz_out, int64_t cap, int64_t* n_out);
+/* Device time in milliseconds from HIP events on the index's stream: [0] the last traversal of these queries  [1] the last mask  [2] the last apply
+ * (scan, compaction and build).  Copies are not included. */
+int immesh_knn_last_timing(immesh_cloud_index* ix, float ms[3]);
 
 #ifdef __cplusplus
 }

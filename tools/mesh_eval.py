@@ -50,6 +50,14 @@ One option looks at the cloud first (include/immesh_align.h), off by default:
                             evaluated by iterated closest-face least squares (immesh_align) from the identity, linearised about the cloud's mean, with
                             point or point-to-plane rows, pairs within D (1.0), at most N iterations (30), and move the cloud by the pose found.  The
                             output gains an `align` block: the options, status, iterations, pose and the rms per iteration
+Two options clean the cloud itself before that (include/immesh_nearest.h, the Outliers rule), off by default:
+  --cloud-outliers-knn K MULT | --cloud-outliers-radius R MIN
+                            first of all that reads the cloud, before --align: index the cloud, drop the points whose mean distance to their K
+                            nearest neighbours within --max-dist exceeds mu + MULT sigma over the cloud (immesh_knn_cloud,
+                            immesh_cloud_outliers_statistical) and / or the points with fewer than MIN others within R (immesh_radius_count_cloud,
+                            immesh_cloud_outliers_radius), shrink the index on the device (immesh_cloud_index_apply_outliers) and fetch the kept
+                            points (immesh_cloud_index_points), so that accuracy, alignment and completeness see one cloud.  The output gains a
+                            `cloud_outliers` block: the arguments, mu, sigma, the threshold and the counts
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
@@ -60,6 +68,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--smooth N_STEPS [--smooth-lambda L] [--smooth-mu M] [--smooth-border fixed|along|free]]
                               [--remove-self-intersections] [--self-intersections] [--max-candidates N] [--manifold]
                               [--align point|plane [--align-max-dist D] [--align-iters N]]
+                              [--cloud-outliers-knn K MULT] [--cloud-outliers-radius R MIN]
 """
 import argparse
 import json
@@ -230,6 +239,30 @@ def align_cloud(h, cloud, mode, max_dist=1.0, max_iters=30):
                    "rms": hist[:, 1].tolist()}
 
 
+def filter_cloud(h, cloud, knn=None, radius=None, max_dist=1.0):
+    """the stray points of a ground-truth cloud taken out on the device, statistical rule first when both are given: knn = (K, MULT) keeps the points
+    whose mean distance to their K nearest neighbours (within max_dist) is at most mu + MULT sigma; radius = (R, MIN) keeps the points with at least
+    MIN others within R -> (the kept points as the index holds them, the rules' arguments and counts)"""
+    cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    out = {"points_before": len(cloud)}
+    h.cloud_index_build(cloud)
+    if knn is not None:
+        k, mult = int(knn[0]), float(knn[1])
+        h.knn_cloud(k, max_dist, want=())
+        st = h.cloud_outliers_statistical(mult)
+        h.cloud_index_apply_outliers()
+        out["knn"] = {"k": k, "mult": mult, "max_dist": max_dist, **{n: v for n, v in st.items() if n != "keep"}}
+    if radius is not None:
+        r, min_neighbours = float(radius[0]), int(radius[1])
+        h.radius_count_cloud(r)
+        st = h.cloud_outliers_radius(min_neighbours)
+        h.cloud_index_apply_outliers()
+        out["radius"] = {"radius": r, "min_neighbours": min_neighbours, **{n: v for n, v in st.items() if n != "keep"}}
+    kept = h.cloud_index_points()                        # the accuracy half runs on the same cloud as the completeness half
+    out["points_kept"] = len(kept)
+    return kept, out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cloud", required=True, help="ground-truth points, .npy of shape (n, 3) or (n, >= 3)")
@@ -260,7 +293,15 @@ def main():
     ap.add_argument("--align", choices=sorted(ALIGN_MODES), default=None, help="refine the cloud's pose against the evaluated mesh first (ICP with point or plane rows)")
     ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="with --align: pairs farther apart do not take part (1.0)")
     ap.add_argument("--align-iters", type=int, default=None, metavar="N", help="with --align: at most N iterations (30)")
+    ap.add_argument("--cloud-outliers-knn", type=float, nargs=2, default=None, metavar=("K", "MULT"),
+                    help="drop the cloud points whose mean distance to their K nearest neighbours exceeds mu + MULT sigma, before everything that reads the cloud")
+    ap.add_argument("--cloud-outliers-radius", type=float, nargs=2, default=None, metavar=("R", "MIN"),
+                    help="drop the cloud points with fewer than MIN others within R, before everything that reads the cloud")
     args = ap.parse_args()
+    if args.cloud_outliers_knn is not None and not (args.cloud_outliers_knn[0] == int(args.cloud_outliers_knn[0]) and 1 <= args.cloud_outliers_knn[0] <= 64):
+        ap.error("--cloud-outliers-knn K MULT: K is an integer in 1 .. 64")
+    if args.cloud_outliers_radius is not None and not (args.cloud_outliers_radius[1] == int(args.cloud_outliers_radius[1]) and args.cloud_outliers_radius[1] >= 0):
+        ap.error("--cloud-outliers-radius R MIN: MIN is an integer, not negative")
     if args.align is None and (args.align_max_dist is not None or args.align_iters is not None):
         ap.error("--align-max-dist and --align-iters go with --align {point,plane}")
     if args.max_candidates is not None and not (args.remove_self_intersections or args.self_intersections):
@@ -303,6 +344,8 @@ def main():
             extra["topology"] = topology(h)
         if args.self_intersections:
             extra["intersections"] = self_intersections(h, max_candidates)
+        if args.cloud_outliers_knn is not None or args.cloud_outliers_radius is not None:   # the strays leave before the alignment weighs them
+            cloud, extra["cloud_outliers"] = filter_cloud(h, cloud, args.cloud_outliers_knn, args.cloud_outliers_radius, args.max_dist)
         if args.align:                                    # the cloud is moved before anything else reads it
             cloud, extra["align"] = align_cloud(h, cloud, args.align, 1.0 if args.align_max_dist is None else args.align_max_dist,
                                                 30 if args.align_iters is None else args.align_iters)
