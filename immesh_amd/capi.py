@@ -263,6 +263,7 @@ class OrientStats(C.Structure):
 
 assert C.sizeof(OrientStats) == 72
 ORIENT_FIRST, ORIENT_FEWEST, ORIENT_VIEWPOINT = 0, 1, 2
+NORMALS_CANONICAL, NORMALS_VIEWPOINT = 0, 1                                          # include/immesh_normals.h: the sign of a cloud normal
 
 
 class HolesStats(C.Structure):
@@ -1159,6 +1160,78 @@ class HotPath:
         f = self.lib.immesh_knn_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
         ms = (C.c_float * 3)()
         self._check(f(self.cloud_index(), ms), "knn_last_timing")
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # -- normals of the cloud and their agreement with the mesh (include/immesh_normals.h) ------------------------------------------------------------
+    @staticmethod
+    def _pair_counts(counts):
+        return dict(zip(("pairs", "opposed", "no_pair", "not_finite"), (int(v) for v in counts)))
+
+    def cloud_normals(self, k, max_dist, min_ratio=0.0, mode=NORMALS_CANONICAL, viewpoint=None, want=("normal", "curvature", "eig", "count", "status")):
+        """immesh_cloud_normals: a normal per point of the index's cloud from its k nearest neighbours -> dict of the wanted outputs: normal (n, 3)
+        float32 (NaN without one), curvature (n,) float64, eig (n, 3) float64 (smallest, middle, largest), count (n,) int32, status (n,) uint8
+        (0 a normal, 1 too few neighbours, 3 line-like, 2 not finite), and always with_normal, too_few, line_like, not_finite; the normals stay on
+        the device for the agreement calls"""
+        f = self.lib.immesh_cloud_normals
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 7; f.restype = C.c_int
+        n = self._cloud_index_given()
+        out = {"normal": np.empty((n, 3), np.float32), "curvature": np.empty(n, np.float64), "eig": np.empty((n, 3), np.float64),
+               "count": np.empty(n, np.int32), "status": np.empty(n, np.uint8)}
+        out = {key: v for key, v in out.items() if key in want}
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        counts = np.zeros(4, np.int64)
+        self._check(f(self.cloud_index(), k, max_dist, min_ratio, mode, _ptr(vp), *[_ptr(out.get(key)) for key in ("normal", "curvature", "eig", "count", "status")],
+                      _ptr(counts)), "cloud_normals")
+        out.update(zip(("with_normal", "too_few", "line_like", "not_finite"), (int(v) for v in counts)))
+        return out
+
+    def cloud_normals_get(self):
+        """immesh_cloud_normals_get: the last normals as they lie on the device -> (normal (n, 3) float32, status (n,) uint8)"""
+        f = self.lib.immesh_cloud_normals_get; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.cloud_index(), None, None, 0, C.byref(n)), "cloud_normals_get")
+        normal, status = np.empty((n.value, 3), np.float32), np.empty(n.value, np.uint8)
+        self._check(f(self.cloud_index(), _ptr(normal), _ptr(status), n.value, C.byref(n)), "cloud_normals_get")
+        return normal, status
+
+    def normals_agree_samples(self, fetch=True):
+        """immesh_normals_agree_samples: the face normal of every sample of the caster against the normal of its nearest cloud point (the last
+        nearest_samples) -> dict: agree (n,) float32 (NaN without a pair; with fetch), pairs, opposed, no_pair, not_finite"""
+        f = self.lib.immesh_normals_agree_samples; f.argtypes = [C.c_void_p] * 4; f.restype = C.c_int
+        agree = None
+        if fetch:
+            g = self.lib.immesh_mesh_sample_count; g.argtypes = [C.c_void_p, C.c_void_p]; g.restype = C.c_int
+            n = C.c_int64(0)
+            self._check(g(self.raycaster(), C.byref(n)), "mesh_sample_count")
+            agree = np.empty(n.value, np.float32)
+        counts = np.zeros(4, np.int64)
+        self._check(f(self.cloud_index(), self.raycaster(), _ptr(agree), _ptr(counts)), "normals_agree_samples")
+        return dict({"agree": agree} if fetch else {}, **self._pair_counts(counts))
+
+    def normals_agree_cloud(self, max_dist, fetch=True):
+        """immesh_normals_agree_cloud: the normal of every cloud point against the normal of its closest face within max_dist -> dict: agree (n,)
+        float32 and face (n,) int32 (with fetch), pairs, opposed, no_pair, not_finite"""
+        f = self.lib.immesh_normals_agree_cloud; f.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 3; f.restype = C.c_int
+        n = self._cloud_index_given()
+        agree, face = (np.empty(n, np.float32), np.empty(n, np.int32)) if fetch else (None, None)
+        counts = np.zeros(4, np.int64)
+        self._check(f(self.cloud_index(), self.raycaster(), max_dist, _ptr(agree), _ptr(face), _ptr(counts)), "normals_agree_cloud")
+        return dict({"agree": agree, "face": face} if fetch else {}, **self._pair_counts(counts))
+
+    def normals_agree_stats(self, bin_width, n_bins):
+        """immesh_normals_agree_reduce over the index's last agreement -> (ClosestStats, histogram (n_bins,) int64); n_with_face reads: pairs, and
+        mean is the normal consistency"""
+        f = self.lib.immesh_normals_agree_reduce; f.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(ClosestStats), C.c_void_p]; f.restype = C.c_int
+        st = ClosestStats()
+        hist = np.zeros(max(int(n_bins), 0) if int(n_bins) <= (1 << 20) else 0, np.int64)      # (a bad size is the library's to reject)
+        self._check(f(self.cloud_index(), bin_width, n_bins, C.byref(st), _ptr(hist)), "normals_agree_reduce")
+        return st, hist
+
+    def normals_timing(self):
+        """device milliseconds of the last (normals launch, agreement launch, reduction)"""
+        f = self.lib.immesh_normals_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 3)()
+        self._check(f(self.cloud_index(), ms), "normals_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
 
     # -- the topology of the caster's snapshot (include/immesh_topology.h) ----------------------------------------------------------------------------

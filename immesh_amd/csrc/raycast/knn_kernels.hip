@@ -2,7 +2,7 @@
 // Outliers rules, is the exact contract these kernels implement).
 //   knn       one query per lane on the offering walk of raycast_dev.hpp (dq_walk_offer) over the index's hierarchy; the lane keeps the k best
 //             (D, index) pairs as a sorted insertion list in private memory beside the walk's stack; the walk's bound is r2 until the list is
-//             full and its k-th D from then on.  The list's capacity is a compile-time size (KN_SIZES) so that a small k does not pay for 64 slots.
+//             full and its k-th D from then on.  The list and the choice of its compile-time capacity (KN_SIZES) live in knn_dev.hpp, which the normals share.
 //             Cloud mode reads query i from the cloud itself, never offers index i, and folds the mean of the list's distances into the same lane.
 //   count     the same walk with r2 as its bound throughout; the sink counts.
 //   masks     one lane per cloud point; the four counts are integer folds (pass_dev.hpp), one atomic per workgroup and count.
@@ -11,48 +11,16 @@
 // stores only: no floating-point atomic, no cross-lane operation on a distance.
 #include "raycast.hpp"
 #include "raycast_dev.hpp"
+#include "knn_dev.hpp"
 #include "pass_dev.hpp"
 
 namespace {
-
-// the D rule for cloud point j
-__device__ __forceinline__ double kn_dist(const float* __restrict__ cloud, const double* p, int32_t j) {
-    const float* c = cloud + 3 * (int64_t)j;
-    const double e0 = (double)c[0] - p[0], e1 = (double)c[1] - p[1], e2 = (double)c[2] - p[2];
-    return (e0 * e0 + e1 * e1) + e2 * e2;
-}
 
 // query i of a launch: mode 2 reads cloud point i where it lies (no frame); false when the query has no candidates by rule
 template <int MODE>
 __device__ __forceinline__ bool kn_query(const RcFrame& fr, const float* __restrict__ pts, const float* __restrict__ cloud, int64_t i, double* p) {
     return dq_point(fr, MODE == 1, MODE == 2 ? cloud : pts, i, p);
 }
-
-// the k best (D, index) pairs seen so far, ascending; slots [0, n) are filled.  offer() is the walk's leaf.
-template <int CAP>
-struct KnList {
-    const float* __restrict__ cloud;
-    const double* p;
-    double r2;
-    int32_t k, skip, n;
-    double d[CAP];
-    int32_t id[CAP];
-    __device__ __forceinline__ double bound() const { return n == k ? d[k - 1] : r2; }
-    __device__ __forceinline__ double offer(int32_t j) {
-        if (j == skip) return bound();
-        const double D = kn_dist(cloud, p, j);
-        if (!(D <= r2)) return bound();
-        if (n == k && !(D < d[k - 1] || (D == d[k - 1] && j < id[k - 1]))) return d[k - 1];   // not among the k best under (D, index)
-        int s = n == k ? k - 1 : n;                     // the slot that opens: the last one when full (its pair leaves), else the next free one
-        while (s > 0 && (d[s - 1] > D || (d[s - 1] == D && id[s - 1] > j))) {
-            d[s] = d[s - 1]; id[s] = id[s - 1];
-            s--;
-        }
-        d[s] = D; id[s] = j;
-        if (n < k) n++;
-        return bound();
-    }
-};
 
 struct KnCounter {
     const float* __restrict__ cloud;
@@ -152,11 +120,10 @@ __global__ void __launch_bounds__(RC_BLOCK) kn_compact_kernel(const float* __res
 template <int MODE>
 void kn_knn_sized(hipStream_t s, const RcFrame& fr, const float* pts, int64_t n, int32_t k, double r2, const float* cloud, const RcNode* nodes, int64_t n_in,
                   int32_t* count, int32_t* index, double* d2, double* mean, uint8_t* status) {
-    const unsigned g = rc_grid(n);
-    // KN_SIZES: the list's capacities
-    if (k <= 4) kn_knn_kernel<MODE, 4><<<g, RC_BLOCK, 0, s>>>(fr, pts, n, k, r2, cloud, nodes, n_in, count, index, d2, mean, status);
-    else if (k <= 16) kn_knn_kernel<MODE, 16><<<g, RC_BLOCK, 0, s>>>(fr, pts, n, k, r2, cloud, nodes, n_in, count, index, d2, mean, status);
-    else kn_knn_kernel<MODE, 64><<<g, RC_BLOCK, 0, s>>>(fr, pts, n, k, r2, cloud, nodes, n_in, count, index, d2, mean, status);
+    // KN_SIZES (knn_dev.hpp): the list's capacities
+    kn_sized(k, [&](auto cap) {
+        kn_knn_kernel<MODE, decltype(cap)::value><<<rc_grid(n), RC_BLOCK, 0, s>>>(fr, pts, n, k, r2, cloud, nodes, n_in, count, index, d2, mean, status);
+    });
 }
 
 }  // namespace

@@ -98,6 +98,7 @@ int immesh_cloud_index_build(immesh_cloud_index* x, const float* xyz, int64_t n_
     (void)hipSetDevice(c->cfg.device);
     x->built = false; x->q.have = false;
     x->kn.changed();   // neighbour results and masks belong to the cloud they were made on
+    x->nr.changed();   // and so do the normals
     int rc;
     if ((rc = rc_grow(c, "cloud_index", x->pts, (size_t)n_pts * 12))) return rc;
     if (n_pts > 0) HIPCHK(c, hipMemcpyAsync(x->pts.p, xyz, (size_t)n_pts * 12, hipMemcpyHostToDevice, x->s));
@@ -133,6 +134,7 @@ int immesh_nearest_points(immesh_cloud_index* x, const immesh_ray_frame* frame, 
     const size_t n = (size_t)n_q;
     if ((rc = rc_grow(c, "cloud_index", x->q_pts, n * 12))) return rc;
     if ((rc = cn_grow_results(x, n))) return rc;
+    x->q_rc = nullptr;
     if (n_q > 0) HIPCHK(c, hipMemcpyAsync(x->q_pts.p, pts, n * 12, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(x->ev[2], s));
     cn_launch_nearest(s, fr, frame != nullptr, (const float*)x->q_pts.p, n_q, max_dist * max_dist, (const float*)x->pts.p, (const RcNode*)x->tree.nodes.p, x->tree.n_in,
@@ -153,6 +155,7 @@ int immesh_nearest_samples(immesh_cloud_index* x, immesh_raycaster* r, double ma
     hipStream_t s = x->s;
     x->q.have = false;
     const int64_t n_q = r->sm.n;
+    x->q_rc = r; x->q_gen = r->sm.gen;   // which samples this query reads (the agreement of include/immesh_normals.h asks)
     if ((rc = cn_grow_results(x, (size_t)n_q))) return rc;
     HIPCHK(c, hipStreamWaitEvent(s, r->sm.done, 0));   // the samples are complete before the traversal reads them
     HIPCHK(c, hipEventRecord(x->ev[2], s));
@@ -215,6 +218,7 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
     (void)hipEventElapsedTime(&q.ms[1], q.ev[2], q.ev[3]);
     q.n = total;
     q.have = true;
+    q.gen++;
     if (n_out) *n_out = total;
     if ((!xyz_out && !face_out) || total == 0) return 0;
     if (cap < total) {

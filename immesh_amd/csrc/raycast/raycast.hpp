@@ -177,6 +177,7 @@ struct RcSample {
     int64_t* h_total = nullptr;                                // pinned
     bool have = false;                                         // samples of the current snapshot exist
     int64_t n = 0;
+    uint64_t gen = 0;                                          // counts the samplings: a query of the samples remembers which one it read
     float ms[2] = {0.0f, 0.0f};
     ~RcSample() {
         rc_destroy_events(ev, 4);
@@ -364,6 +365,26 @@ struct RcKnn {
     }
 };
 
+// the normals of the index's cloud and their agreement with a caster's face normals (include/immesh_normals.h; normals_host.cpp): allocated at the
+// first call of one of them, never before.  A build and an apply drop the normals and with them the agreement.
+struct RcNormals {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // normals, agreement, reduction: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: the four counts of the last launch
+    RcBuf normal, status;                                      // the last normals: 3 floats and a uint8 per cloud point (the agreement reads them)
+    RcBuf curv, eig, cnt;                                      // the last normals call's other outputs
+    RcBuf dcnt;                                                // the four device counts
+    RcBuf agree, face;                                         // the last agreement: s as a float; the cloud direction's closest face
+    RcDist a;                                                  // the last agreement as the reduction reads it: dist = |s|, status 0 a pair / 1 none / 2 not finite
+    bool have = false;
+    int64_t n = 0;                                             // the cloud's size when the normals were made
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    void changed() { have = false; a.have = false; }
+    ~RcNormals() {
+        rc_destroy_events(ev, 6);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi, built by the same rc_tree_build, one point per leaf.
 struct immesh_cloud_index {
     immesh_ctx* ctx = nullptr;
@@ -374,10 +395,13 @@ struct immesh_cloud_index {
     RcTree tree;
     RcBuf q_pts;                                                                   // the last query's host-copied points
     RcDist q;                                                                      // id: the cloud point
+    const immesh_raycaster* q_rc = nullptr;                                        // the last query read this caster's samples (nullptr: host points)
+    uint64_t q_gen = 0;                                                            // ... of this sampling
     bool built = false;
     int64_t n_pts = 0;
     float ms[3] = {0.0f, 0.0f, 0.0f};
     RcKnn kn;
+    RcNormals nr;
 };
 
 // nearest cloud point of every query; status[i] as rc_launch_closest writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
@@ -406,3 +430,18 @@ void kn_launch_mask_radius(hipStream_t s, const int32_t* count, const uint8_t* s
                            unsigned long long* cnt);
 // the apply's compaction behind the exclusive scan of flag: out[off[i]] = pts[i], kept[off[i]] = i for the kept points (off[i] checked against n_kept)
 void kn_launch_compact(hipStream_t s, const float* pts, const int32_t* flag, const int32_t* off, int64_t n, int64_t n_kept, float* out, int32_t* kept);
+
+// ---- normals of the cloud and their agreement with face normals (include/immesh_normals.h, the Normals / Agreement rules): normals_host.cpp
+// one cloud point per lane: normal[3 i], curv[i], eig[3 i], count[i], status[i] (0 a normal, 1 too few, 3 line-like, 2 not finite); cnt[0 .. 3] (zeroed
+// by the caller) += with a normal, too few, line-like, not finite.  viewpoint == nullptr: the canonical sign alone.  No list is stored.
+void nr_launch_normals(hipStream_t s, int64_t n, int32_t k, double r2, double min_ratio, const double* viewpoint, const float* cloud, const RcNode* nodes,
+                       int64_t n_in, float* normal, double* curv, double* eig, int32_t* count, uint8_t* status, unsigned long long* cnt);
+// agree[i] = (float)s or a quiet NaN, abs_agree[i] = |agree[i]| (-1 without a pair), status[i] = 0 a pair, 1 no pair, 2 the cloud point is not finite;
+// cnt[0 .. 3] (zeroed by the caller) += pairs, opposed pairs, no pair, not finite.  Cloud direction: face[i] = the closest face of a point with a normal
+void nr_launch_agree_cloud(hipStream_t s, const float* cloud, const float* normal, const uint8_t* nstatus, int64_t n, double r2, const float* vtx, int64_t n_vtx,
+                           const int32_t* faces, int64_t n_faces, const RcNode* nodes, int64_t n_in, float* agree, float* abs_agree, int32_t* face,
+                           uint8_t* status, unsigned long long* cnt);
+// samples direction: sample j has face sface[j] and nearest cloud point index[j] (-1: none); index is checked against n_pts, sface against n_faces
+void nr_launch_agree_samples(hipStream_t s, const int32_t* sface, const int32_t* index, int64_t n, const float* normal, const uint8_t* nstatus, int64_t n_pts,
+                             const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces, float* agree, float* abs_agree, uint8_t* status,
+                             unsigned long long* cnt);

@@ -58,6 +58,15 @@ Two options clean the cloud itself before that (include/immesh_nearest.h, the Ou
                             immesh_cloud_outliers_radius), shrink the index on the device (immesh_cloud_index_apply_outliers) and fetch the kept
                             points (immesh_cloud_index_points), so that accuracy, alignment and completeness see one cloud.  The output gains a
                             `cloud_outliers` block: the arguments, mu, sigma, the threshold and the counts
+One option compares orientations as well (include/immesh_normals.h), off by default:
+  --normals K [--normals-max-dist D] [--normals-min-ratio R] [--viewpoint X Y Z]
+                            after the outlier options and --align, behind the distances: a normal per ground-truth point from its K nearest
+                            neighbours within D (--max-dist by default; a neighbourhood whose middle eigenvalue is not above R times its largest
+                            is line-like and gets none; with --viewpoint the normals face that point), then |cos| between that normal and the
+                            mesh's face normal in both directions (immesh_cloud_normals, immesh_normals_agree_cloud, immesh_normals_agree_samples,
+                            immesh_normals_agree_reduce).  The output gains normal_consistency_accuracy (every ground-truth point with its closest
+                            face), normal_consistency_completeness (every sample with its nearest ground-truth point), normal_consistency (their
+                            mean) and a `normals` block: the arguments, the normals' counts, the pairs and the opposed share of each direction
 The mesh is a PLY written by immesh_save_ply (binary little-endian: float x y z; list uchar int vertex_indices), or the live mesh of a context:
 evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast_build_mesh() / h.raycast_build_triangles()).
 
@@ -69,6 +78,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--remove-self-intersections] [--self-intersections] [--max-candidates N] [--manifold]
                               [--align point|plane [--align-max-dist D] [--align-iters N]]
                               [--cloud-outliers-knn K MULT] [--cloud-outliers-radius R MIN]
+                              [--normals K [--normals-max-dist D] [--normals-min-ratio R]]
 """
 import argparse
 import json
@@ -115,9 +125,25 @@ def _signed(dist, side):
             "share_behind": behind / n if n else 0.0, "share_in_plane": in_plane / n if n else 0.0, "signed_mean": mean}
 
 
-def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0, signed=False):
+def normal_consistency(h, max_dist, k, normals_max_dist=None, min_ratio=0.0, viewpoint=None):
+    """h: a HotPath whose index holds the ground-truth cloud and whose last nearest_samples query read the caster's current samples (evaluate leaves
+    both so) -> dict: the three consistencies and the `normals` block.  A direction without a pair has consistency 0"""
+    nd = max_dist if normals_max_dist is None else normals_max_dist
+    made = h.cloud_normals(k, nd, min_ratio, capi.NORMALS_CANONICAL if viewpoint is None else capi.NORMALS_VIEWPOINT, viewpoint, want=())
+    block = {"k": k, "max_dist": nd, "min_ratio": min_ratio, "viewpoint": None if viewpoint is None else [float(x) for x in viewpoint], **made}
+    means = {}
+    for name in ("completeness", "accuracy"):                                   # each reduced before the other replaces it
+        counts = h.normals_agree_samples(fetch=False) if name == "completeness" else h.normals_agree_cloud(max_dist, fetch=False)
+        st, _ = h.normals_agree_stats(1.0, 1)
+        means[name] = st.mean
+        block[name] = {**counts, "opposed_share": counts["opposed"] / counts["pairs"] if counts["pairs"] else 0.0}
+    return {"normal_consistency_accuracy": means["accuracy"], "normal_consistency_completeness": means["completeness"],
+            "normal_consistency": 0.5 * (means["accuracy"] + means["completeness"]), "normals": block}
+
+
+def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0, signed=False, normals=None):
     """h: a HotPath with a built caster; cloud (n, 3) float32 ground truth -> dict; signed: add the `signed` block (it means something once the mesh
-    has been oriented)"""
+    has been oriented); normals: the keyword arguments of normal_consistency (k, normals_max_dist, min_ratio, viewpoint) to add its figures"""
     cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
     got = h.closest_points(cloud, max_dist, want=("dist", "side") if signed else ())
     extra = {"signed": _signed(got["dist"], got["side"])} if signed else {}
@@ -127,6 +153,8 @@ def evaluate(h, cloud, tau=0.05, max_dist=1.0, density=400.0, seed=0, signed=Fal
     h.nearest_samples(max_dist, want=())
     com = _side(*h.nearest_stats(tau, 1))
     p, r = com["share_within_tau"], acc["share_within_tau"]
+    if normals is not None:
+        extra.update(normal_consistency(h, max_dist, **normals))
     return {"tau": tau, "max_dist": max_dist, "density": density, "seed": seed, "samples": n_samples, "cloud_points": n_cloud, "cloud_points_indexed": n_in,
             "accuracy": acc, "completeness": com, "chamfer": acc["mean"] + com["mean"], "precision": p, "recall": r,
             "f_score": (2.0 * p * r / (p + r)) if p + r > 0 else 0.0, **extra}
@@ -297,7 +325,14 @@ def main():
                     help="drop the cloud points whose mean distance to their K nearest neighbours exceeds mu + MULT sigma, before everything that reads the cloud")
     ap.add_argument("--cloud-outliers-radius", type=float, nargs=2, default=None, metavar=("R", "MIN"),
                     help="drop the cloud points with fewer than MIN others within R, before everything that reads the cloud")
+    ap.add_argument("--normals", type=int, default=None, metavar="K", help="add the normal consistency: cloud normals from the K nearest neighbours (2 .. 64)")
+    ap.add_argument("--normals-max-dist", type=float, default=None, metavar="D", help="with --normals: neighbours within D (--max-dist)")
+    ap.add_argument("--normals-min-ratio", type=float, default=None, metavar="R", help="with --normals: no normal where the middle eigenvalue is not above R times the largest (0)")
     args = ap.parse_args()
+    if args.normals is None and (args.normals_max_dist is not None or args.normals_min_ratio is not None):
+        ap.error("--normals-max-dist and --normals-min-ratio go with --normals K")
+    if args.normals is not None and not 2 <= args.normals <= 64:
+        ap.error("--normals K: K is an integer in 2 .. 64")
     if args.cloud_outliers_knn is not None and not (args.cloud_outliers_knn[0] == int(args.cloud_outliers_knn[0]) and 1 <= args.cloud_outliers_knn[0] <= 64):
         ap.error("--cloud-outliers-knn K MULT: K is an integer in 1 .. 64")
     if args.cloud_outliers_radius is not None and not (args.cloud_outliers_radius[1] == int(args.cloud_outliers_radius[1]) and args.cloud_outliers_radius[1] >= 0):
@@ -317,8 +352,8 @@ def main():
         ap.error("--simplify-mode and --keep-duplicate-faces go with --weld or --simplify CELL")
     if args.fill_max_diagonal and not args.fill_holes:
         ap.error("--fill-max-diagonal D goes with --fill-holes")
-    if (args.orient == "viewpoint") != (args.viewpoint is not None):
-        ap.error("--viewpoint X Y Z goes with --orient viewpoint, and only with it")
+    if (args.orient == "viewpoint" and args.viewpoint is None) or (args.viewpoint is not None and args.orient != "viewpoint" and args.normals is None):
+        ap.error("--viewpoint X Y Z goes with --orient viewpoint or --normals K, and only with them")
     cloud = np.load(args.cloud)[:, :3]
     vtx, faces = read_ply(args.ply)
     h = capi.HotPath(capi.load_hip_library(), capi.avia_config(cap_root_voxels=1 << 12, cap_scan_points=200000, cap_vertices=1 << 18, cap_triangles=1 << 20), "immesh_")
@@ -349,7 +384,9 @@ def main():
         if args.align:                                    # the cloud is moved before anything else reads it
             cloud, extra["align"] = align_cloud(h, cloud, args.align, 1.0 if args.align_max_dist is None else args.align_max_dist,
                                                 30 if args.align_iters is None else args.align_iters)
-        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient)), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
+        normals = None if args.normals is None else dict(k=args.normals, normals_max_dist=args.normals_max_dist, min_ratio=args.normals_min_ratio or 0.0,
+                                                         viewpoint=args.viewpoint)
+        out = dict(evaluate(h, cloud, args.tau, args.max_dist, args.density, args.seed, signed=bool(args.orient), normals=normals), mesh={"vertices": sizes[0], "faces": sizes[1], "faces_in_tree": sizes[2]},
                    **extra)
     finally:
         h.close()
