@@ -169,9 +169,15 @@ static int ds_copy_out(immesh_ctx* c, int32_t cnt, float* out_xyz, int32_t cap_o
     HIPCHK(c, hipStreamSynchronize(c->stream_pre));
     return 0;
 }
+// a leaf the grid can be formed with: positive (a NaN is not), and float32(1 / leaf) -- the factor every cell index is taken with -- finite and not zero
+static bool ds_leaf_ok(double leaf) {
+    if (!(leaf > 0)) return false;
+    const float inv = (float)(1.0 / leaf);
+    return std::isfinite(inv) && inv > 0.f;
+}
 // pcl::VoxelGrid stand-in on the device (the stage before lio_state_estimation, src/voxel_mapping.cpp:1888-1891)
 int immesh_downsample(immesh_ctx* c, const float* pts, int32_t n, int32_t stride, double leaf, float* out_xyz, int32_t cap_out, int32_t* n_out) {
-    if (!c || !pts || n <= 0 || n > c->cap_scan || (stride != 3 && stride != 4) || leaf <= 0 || !n_out) { if (c) c->err = "bad arguments"; return IMMESH_E_INVAL; }
+    if (!c || !pts || n <= 0 || n > c->cap_scan || (stride != 3 && stride != 4) || !ds_leaf_ok(leaf) || !n_out) { if (c) c->err = "bad arguments"; return IMMESH_E_INVAL; }
     // the synchronous call and an asynchronous job share the pinned parameter block, the leaf table, the counters and the ticket word: between
     // immesh_downsample_begin and immesh_downsample_end the job's kernels still read them
     if (c->dsa.active) { c->err = "immesh_downsample: an asynchronous job is in flight (collect it with immesh_downsample_end first)"; return IMMESH_E_INVAL; }
@@ -255,7 +261,7 @@ static int ds_job_launch(immesh_ctx* c) {
     return 0;
 }
 int immesh_downsample_begin(immesh_ctx* c, const float* pts, int32_t n, int32_t stride, double leaf) {
-    if (!c || !pts || n <= 0 || n > c->cap_scan || (stride != 3 && stride != 4) || leaf <= 0) { if (c) c->err = "bad arguments"; return IMMESH_E_INVAL; }
+    if (!c || !pts || n <= 0 || n > c->cap_scan || (stride != 3 && stride != 4) || !ds_leaf_ok(leaf)) { if (c) c->err = "bad arguments"; return IMMESH_E_INVAL; }
     if (c->dsa.active) { c->err = "immesh_downsample_begin: the previous job has not been collected (immesh_downsample_end)"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
     ProfBind _pb(c);

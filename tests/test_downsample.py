@@ -49,6 +49,7 @@ def test_device_downsample_bit_exact(oracle_lib, hip_lib):
         d = torch.from_numpy(np.ascontiguousarray(pts)).cuda()                        # device-resident input, result kept on the device
         _, n2 = h.downsample(d.data_ptr(), leaf, n=len(pts), stride=4, to_host=False)
         assert n2 == n
+        np.testing.assert_array_equal(fetch_device(h.downsample_result_ptr(), (n2, 3)), ref)
     # the device-resident result feeds the registration without leaving HBM
     extT = np.array(list(cfg.extT))
     R0, t0 = synth.trajectory_pose(0)
