@@ -1162,6 +1162,46 @@ class HotPath:
         self._check(f(self.cloud_index(), ms), "knn_last_timing")
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    # -- Euclidean clusters of the cloud index (include/immesh_nearest.h, the Clusters rule) ----------------------------------------------------------
+    def cloud_clusters(self, radius, min_neighbours=0, want=("label", "kind")):
+        """immesh_cloud_clusters: DBSCAN over the index's cloud -> dict of the wanted outputs: label (n,) int32 (the cluster's number, -1: noise or not
+        finite), kind (n,) uint8 (0 core, 1 border, 2 noise, 3 not finite), and always counts (core, border, noise, not_finite as a dict) and
+        n_clusters; the clusters stay on the device for cloud_clusters_table and cloud_clusters_select"""
+        f = self.lib.immesh_cloud_clusters; f.argtypes = [C.c_void_p, C.c_double, C.c_int64] + [C.c_void_p] * 4; f.restype = C.c_int
+        n = self._cloud_index_given()
+        out = {key: v for key, v in (("label", np.empty(n, np.int32)), ("kind", np.empty(n, np.uint8))) if key in want}
+        counts, nc = np.zeros(4, np.int64), C.c_int64(0)
+        self._check(f(self.cloud_index(), radius, min_neighbours, _ptr(out.get("label")), _ptr(out.get("kind")), _ptr(counts), C.byref(nc)), "cloud_clusters")
+        out["counts"] = dict(zip(("core", "border", "noise", "not_finite"), (int(v) for v in counts)))
+        out["n_clusters"] = nc.value
+        return out
+
+    def cloud_clusters_table(self):
+        """immesh_cloud_clusters_table -> dict: first, n_points, n_core (n_clusters,) int32, box (n_clusters, 6) float32 (lo xyz, hi xyz)"""
+        f = self.lib.immesh_cloud_clusters_table; f.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]; f.restype = C.c_int
+        n = C.c_int64(0)
+        self._check(f(self.cloud_index(), None, None, None, None, 0, C.byref(n)), "cloud_clusters_table")
+        n = n.value
+        out = dict(first=np.empty(n, np.int32), n_points=np.empty(n, np.int32), n_core=np.empty(n, np.int32), box=np.empty((n, 6), np.float32))
+        self._check(f(self.cloud_index(), _ptr(out["first"]), _ptr(out["n_points"]), _ptr(out["n_core"]), _ptr(out["box"]), n, None), "cloud_clusters_table")
+        return out
+
+    def cloud_clusters_select(self, min_points=0, max_points=0, keep_largest=0, keep_noise=False):
+        """immesh_cloud_clusters_select over the last cloud_clusters -> dict: kept, dropped (in a cluster and not kept), noise (and not kept),
+        not_finite, keep (n,) bool; the mask is the index's last mask, for cloud_index_apply_outliers"""
+        f = self.lib.immesh_cloud_clusters_select; f.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        counts = np.zeros(4, np.int64)
+        keep = np.zeros(self._cloud_index_given(), np.uint8)
+        self._check(f(self.cloud_index(), min_points, max_points, keep_largest, 1 if keep_noise else 0, _ptr(counts), _ptr(keep)), "cloud_clusters_select")
+        return dict(keep=keep.astype(bool), **dict(zip(("kept", "dropped", "noise", "not_finite"), (int(v) for v in counts))))
+
+    def clusters_timing(self):
+        """device milliseconds of the last cloud_clusters (count and kinds, joins, border walk, numbering and table)"""
+        f = self.lib.immesh_cloud_clusters_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 4)()
+        self._check(f(self.cloud_index(), ms), "cloud_clusters_last_timing")
+        return tuple(float(v) for v in ms)
+
     # -- normals of the cloud and their agreement with the mesh (include/immesh_normals.h) ------------------------------------------------------------
     @staticmethod
     def _pair_counts(counts):

@@ -238,6 +238,7 @@ int immesh_cloud_index_apply_outliers(immesh_cloud_index* x, int32_t* kept_index
     x->built = false; x->q.have = false;
     q.changed();
     x->nr.changed();   // the normals belong to the cloud they were made on
+    x->cl.changed();   // and so do the clusters
     HIPCHK(c, hipEventRecord(q.ev[4], s));
     if (n > 0) rd_scan_i32(s, x->tree.temp.p, x->tree.temp.bytes, (const int32_t*)q.flag.p, (int32_t*)q.off.p, n);
     kn_launch_compact(s, (const float*)x->pts.p, (const int32_t*)q.flag.p, (const int32_t*)q.off.p, n, n_kept, (float*)q.out.p, (int32_t*)q.kept.p);

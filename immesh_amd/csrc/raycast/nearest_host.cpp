@@ -99,6 +99,7 @@ int immesh_cloud_index_build(immesh_cloud_index* x, const float* xyz, int64_t n_
     x->built = false; x->q.have = false;
     x->kn.changed();   // neighbour results and masks belong to the cloud they were made on
     x->nr.changed();   // and so do the normals
+    x->cl.changed();   // and the clusters
     int rc;
     if ((rc = rc_grow(c, "cloud_index", x->pts, (size_t)n_pts * 12))) return rc;
     if (n_pts > 0) HIPCHK(c, hipMemcpyAsync(x->pts.p, xyz, (size_t)n_pts * 12, hipMemcpyHostToDevice, x->s));

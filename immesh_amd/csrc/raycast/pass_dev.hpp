@@ -1,6 +1,6 @@
 // Device primitives shared by the kernels of the passes over the caster's snapshot (topology/, simplify/, smooth/, intersect/, and the sampler and the
-// build of raycast/): the folds of a count into one word, the capped grid, the float keys, the rule "a face counts" and the run kernels of sorted
-// 64-bit keys.  Integers, min / max and bit patterns only: nothing here depends on the order of anything.
+// build of raycast/) and by the clusters of the cloud index: the folds of a count into one word, the capped grid, the float keys, the lock-free
+// union-find, the rule "a face counts" and the run kernels of sorted 64-bit keys.  Integers, min / max and bit patterns only: nothing here depends on the order of anything.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -79,6 +79,39 @@ __device__ __forceinline__ uint32_t pd_key(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float pd_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+// ---- union-find: shared by the mesh topology (topology/) and the clusters of the cloud index (clusters_kernels.hip) ------------------------------
+__device__ __forceinline__ int32_t tp_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x as this lane sees it, halving the path on the way (the grandparent is an ancestor of x and stays one: hooks happen at roots only);
+// -1 when the steps ran out
+__device__ __forceinline__ int32_t tp_find(int32_t* parent, int32_t x, int64_t& steps) {
+    int32_t p = tp_load(parent + x);
+    while (p != x) {
+        const int32_t g = tp_load(parent + p);
+        if (g != p) atomicMin(parent + x, g);
+        x = p;
+        p = g;
+        if (--steps < 0) return -1;
+    }
+    return x;
+}
+
+// false when the bound was hit
+__device__ __forceinline__ bool tp_union(int32_t* parent, int32_t a, int32_t b) {
+    int64_t steps = 2 * ((int64_t)a + (int64_t)b + 2);
+    for (;;) {
+        a = tp_find(parent, a, steps);
+        b = tp_find(parent, b, steps);
+        if (a < 0 || b < 0) return false;
+        if (a == b) return true;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        const int32_t old = atomicCAS(parent + a, a, b);     // the larger root under the smaller
+        if (old == a) return true;
+        a = old;                                             // a was hooked meanwhile, under old < a: go on from there
+        if (--steps < 0) return false;
+    }
+}
 
 // ---- a face counts: its three indices lie in [0, n_vtx) and are pairwise distinct; a vertex is finite: its three floats are ---------------------
 __device__ __forceinline__ bool pd_counts(int64_t a, int64_t b, int64_t c, int64_t n_vtx) {

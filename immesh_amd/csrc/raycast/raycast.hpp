@@ -365,6 +365,28 @@ struct RcKnn {
     }
 };
 
+// the Euclidean clusters of the index's cloud (include/immesh_nearest.h, the Clusters rule; clusters_host.cpp): allocated at the first
+// immesh_cloud_clusters, never before.  Its counts are its own: the index's last Count query stays as it is.  A build and an apply drop the clusters.
+constexpr int CL_ERROR = 4, CL_COUNTERS = 5, CL_PINNED = 8;   // device words: the four counts, the error flag; pinned: those, and [5], [6] the scan's total in two halves
+struct RcClusters {
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count, joins, border walk, numbering, table: begin / end
+    unsigned long long* h_cnt = nullptr;                       // pinned: CL_PINNED words
+    RcBuf cnt, status;                                        // the Count launch's outputs
+    RcBuf core, kind;                                          // per point, uint8: the kind before the border walk (0 core, 2 finite and not core, 3 not finite), and after
+    RcBuf parent, root, flag, num, label;                      // per point, int32: the union-find, the class' root (-1: none), root == self, its scan, the number
+    RcBuf first, npts, ncore, boxkey, box;                     // per cluster: the table (boxkey: six order-preserving keys, box: their floats)
+    RcBuf dcnt, keepc;                                         // CL_COUNTERS device words; a select's per-cluster keep (int32)
+    std::vector<int32_t> h_npts, h_keepc, h_rank;              // a select's one read-back, its answer, the ranking
+    bool have = false;
+    int64_t n_clusters = 0;
+    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    void changed() { have = false; }
+    ~RcClusters() {
+        rc_destroy_events(ev, 10);
+        if (h_cnt) (void)hipHostFree(h_cnt);
+    }
+};
+
 // the normals of the index's cloud and their agreement with a caster's face normals (include/immesh_normals.h; normals_host.cpp): allocated at the
 // first call of one of them, never before.  A build and an apply drop the normals and with them the agreement.
 struct RcNormals {
@@ -402,6 +424,7 @@ struct immesh_cloud_index {
     float ms[3] = {0.0f, 0.0f, 0.0f};
     RcKnn kn;
     RcNormals nr;
+    RcClusters cl;
 };
 
 // nearest cloud point of every query; status[i] as rc_launch_closest writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
@@ -430,6 +453,30 @@ void kn_launch_mask_radius(hipStream_t s, const int32_t* count, const uint8_t* s
                            unsigned long long* cnt);
 // the apply's compaction behind the exclusive scan of flag: out[off[i]] = pts[i], kept[off[i]] = i for the kept points (off[i] checked against n_kept)
 void kn_launch_compact(hipStream_t s, const float* pts, const int32_t* flag, const int32_t* off, int64_t n, int64_t n_kept, float* out, int32_t* kept);
+
+// ---- Euclidean clusters of the cloud (include/immesh_nearest.h, the Clusters rule): clusters_host.cpp; one lane per cloud point throughout
+// core[i] = kind[i] = 3 not finite, 0 finite and count[i] >= min_neighbours (count == nullptr: every finite point), else 2; parent[i] = i, root[i] = -1
+void cl_launch_kind(hipStream_t s, const float* cloud, int64_t n, const int32_t* count, int32_t min_neighbours, uint8_t* core, uint8_t* kind, int32_t* parent,
+                    int32_t* root);
+// the joins: every core lane walks with the bound r2 and unites itself with the core leaves of a lower index within r2; cnt[CL_ERROR] is raised when a
+// union runs out of its steps
+void cl_launch_join(hipStream_t s, const float* cloud, int64_t n, double r2, const RcNode* nodes, int64_t n_in, const uint8_t* core, int32_t* parent,
+                    unsigned long long* cnt);
+// root[i] = the root of core point i's class (its smallest index), flag[i] = core and root[i] == i
+void cl_launch_flatten(hipStream_t s, int64_t n, const uint8_t* core, const int32_t* parent, int32_t* root, int32_t* flag);
+// the lanes with core[i] == 2 walk for their best core leaf under (D, index): kind[i] = 1 and root[i] = that leaf's root, or kind[i] stays 2
+void cl_launch_border(hipStream_t s, const float* cloud, int64_t n, double r2, const RcNode* nodes, int64_t n_in, const uint8_t* core, uint8_t* kind,
+                      int32_t* root);
+// first / npts / ncore / boxkey of n_clusters clusters preset; then, behind the exclusive scan num of flag: label[i] = num[root[i]] or -1, the table's
+// integer folds, cnt[0 .. 3] += core, border, noise, not finite; then box = the keys' floats
+void cl_launch_preset(hipStream_t s, int64_t n_clusters, int32_t* first, int32_t* npts, int32_t* ncore, uint32_t* boxkey);
+void cl_launch_table(hipStream_t s, const float* cloud, int64_t n, const uint8_t* kind, const int32_t* root, const int32_t* num, int64_t n_clusters,
+                     int32_t* label, int32_t* first, int32_t* npts, int32_t* ncore, uint32_t* boxkey, unsigned long long* cnt);
+void cl_launch_unkey(hipStream_t s, int64_t n_clusters, const uint32_t* boxkey, float* box);
+// the Select rule's mask from the per-cluster keep: flag[i] = keep8[i] = keep_i; cnt[0 .. 3] (zeroed by the caller) += kept, in a cluster and not kept,
+// noise and not kept, not finite
+void cl_launch_mask(hipStream_t s, int64_t n, const uint8_t* kind, const int32_t* label, const int32_t* keepc, int64_t n_clusters, int32_t keep_noise,
+                    int32_t* flag, uint8_t* keep8, unsigned long long* cnt);
 
 // ---- normals of the cloud and their agreement with face normals (include/immesh_normals.h, the Normals / Agreement rules): normals_host.cpp
 // one cloud point per lane: normal[3 i], curv[i], eig[3 i], count[i], status[i] (0 a normal, 1 too few, 3 line-like, 2 not finite); cnt[0 .. 3] (zeroed

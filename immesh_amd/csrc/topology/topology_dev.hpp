@@ -18,38 +18,7 @@ __device__ __forceinline__ void tp_count(bool pred, unsigned long long* word) {
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(word, (unsigned long long)__popcll(m));
 }
 
-// ---- union-find ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t tp_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x as this lane sees it, halving the path on the way (the grandparent is an ancestor of x and stays one: hooks happen at roots only);
-// -1 when the steps ran out
-__device__ __forceinline__ int32_t tp_find(int32_t* parent, int32_t x, int64_t& steps) {
-    int32_t p = tp_load(parent + x);
-    while (p != x) {
-        const int32_t g = tp_load(parent + p);
-        if (g != p) atomicMin(parent + x, g);
-        x = p;
-        p = g;
-        if (--steps < 0) return -1;
-    }
-    return x;
-}
-
-// false when the bound was hit
-__device__ __forceinline__ bool tp_union(int32_t* parent, int32_t a, int32_t b) {
-    int64_t steps = 2 * ((int64_t)a + (int64_t)b + 2);
-    for (;;) {
-        a = tp_find(parent, a, steps);
-        b = tp_find(parent, b, steps);
-        if (a < 0 || b < 0) return false;
-        if (a == b) return true;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicCAS(parent + a, a, b);     // the larger root under the smaller
-        if (old == a) return true;
-        a = old;                                             // a was hooked meanwhile, under old < a: go on from there
-        if (--steps < 0) return false;
-    }
-}
+// (the union-find, tp_load / tp_find / tp_union, lives in pass_dev.hpp: the clusters of the cloud index share it)
 
 // forward: i_k < i_(k + 1 mod 3) of half-edge h = 3 f + k
 __device__ __forceinline__ bool tp_forward(const int32_t* __restrict__ faces, int32_t h) {

@@ -76,6 +76,33 @@
  * Validated before any launch: a built index; 1 <= k <= 64; 0 < max_dist and 0 < radius, finite; mult finite and >= 0; min_neighbours in
  * [0, 2^31 - 2]; the matching cloud-mode query made since the last build or apply before an Outliers call; a mask before the apply; the point array
  * and the frame as above; else IMMESH_E_INVAL with text, and the index stays as it was.
+ *
+ * ---- The Clusters rule (Euclidean cluster extraction, DBSCAN; the same arithmetic; exact and free of any order, like everything above) ---------------
+ *   Candidates: as in the Count rule in cloud mode, r2 = radius radius: for cloud point i the other points in the index with D <= r2.  D between two
+ *            cloud points is symmetric bit for bit: (double)c_j - (double)c_i is the exact negation of (double)c_i - (double)c_j, and the squares
+ *            and their sums are the same products in the same order.  So "j is a candidate of i" is a symmetric relation.
+ *            count_i = the number of candidates of i.
+ *   Kind:    (uint8)  3 not finite;  0 core: finite and count_i >= min_neighbours, min_neighbours >= 0;  1 border: finite, not core, and at least one
+ *            candidate is core;  2 noise: finite, not core, and no candidate is core.  With min_neighbours == 0 every finite point is core: that is
+ *            plain Euclidean cluster extraction, and nothing is counted at all.
+ *   Cluster: two core points are joined when each is the other's candidate.  The clusters are the classes of the transitive closure of that relation
+ *            over the core points, and over them only: a border point joins nothing, and two clusters that both reach one stay two.
+ *            A cluster's label is its smallest core index; the clusters are numbered 0 .. n_clusters - 1 by ascending label.
+ *   Border:  a border point gets the cluster of its core candidate that is smallest under (D, index).
+ *   Outputs: label_out[i] (int32) the cluster's number, -1 for noise and for a point that is not finite;  kind_out[i] the kind;
+ *            counts: [0] core  [1] border  [2] noise  [3] not finite; they sum to the cloud's size;  n_clusters the number of clusters.
+ *   Table:   per cluster, by number: first = the label;  n_points = core plus border;  n_core;  box = lo xyz, hi xyz over the floats of all its
+ *            members, compared as values (the sign of a zero is not part of the contract, as in the topology's table).
+ *   Select:  (after the Select rule of the mesh topology's header)  a cluster is kept when n_points >= min_points, and max_points == 0 || n_points <=
+ *            max_points, and keep_largest == 0 or it is among the keep_largest clusters with the most points, counted over ALL clusters, ties to
+ *            the smaller number.  keep_i = point i is in a kept cluster, or (keep_noise != 0 and its kind is noise).
+ *            counts: [0] kept  [1] in a cluster and not kept  [2] noise and not kept  [3] not finite; they sum to the cloud's size.
+ *            The mask becomes the index's last mask: immesh_cloud_index_apply_outliers applies it as it applies the Outliers rules'.
+ * Validated before any launch: a built index; 0 < radius, finite; min_neighbours, min_points, max_points and keep_largest in [0, 2^31 - 2]; a
+ * Clusters call since the last build or apply before a table or a select; cap as in the other fetches; else IMMESH_E_INVAL with text (cap below the
+ * count with an output given: IMMESH_E_CAPACITY), and the index stays as it was.  An empty index gives zero clusters and is no error.
+ * IMMESH_E_INTERNAL (as in the mesh topology's header): a union did not finish within its proven bound of steps (a defect of the library, never of the
+ * input); the clusters are void.
  */
 #ifndef IMMESH_NEAREST_H
 #define IMMESH_NEAREST_H
@@ -145,6 +172,25 @@ int immesh_cloud_index_points(immesh_cloud_index* ix, float* xyz_out, int64_t ca
 /* Device time in milliseconds from HIP events on the index's stream: [0] the last traversal of these queries  [1] the last mask  [2] the last apply
  * (scan, compaction and build).  Copies are not included. */
 int immesh_knn_last_timing(immesh_cloud_index* ix, float ms[3]);
+
+/* The Clusters rule.  IMMESH_E_INTERNAL is the code of the mesh topology's header (the same tokens: the two headers go together in either order). */
+#ifndef IMMESH_E_INTERNAL
+#define IMMESH_E_INTERNAL (-8)
+#endif
+/* The clusters of the index's cloud: label_out one int32 and kind_out one uint8 per cloud point, counts four int64; every output may be NULL.  The
+ * clusters stay on the device for the table and the select.  The index's last Count query is not touched. */
+int immesh_cloud_clusters(immesh_cloud_index* ix, double radius, int64_t min_neighbours, int32_t* label_out, uint8_t* kind_out, int64_t counts[4],
+                          int64_t* n_clusters);
+/* The Table rule over the last clusters: one entry per cluster (box_out six floats); each output may be NULL, n_out too. */
+int immesh_cloud_clusters_table(immesh_cloud_index* ix, int32_t* first_out, int32_t* n_points_out, int32_t* n_core_out, float* box_out, int64_t cap,
+                                int64_t* n_out);
+/* The Select rule over the last clusters: the mask of the cloud on the device, for immesh_cloud_index_apply_outliers.  counts (four int64) and
+ * keep_out (one uint8 per cloud point) may each be NULL. */
+int immesh_cloud_clusters_select(immesh_cloud_index* ix, int64_t min_points, int64_t max_points, int64_t keep_largest, int32_t keep_noise,
+                                 int64_t counts[4], uint8_t* keep_out);
+/* Device time in milliseconds of the last immesh_cloud_clusters from HIP events on the index's stream: [0] the count and the kinds (the kinds alone
+ * when min_neighbours == 0)  [1] the joins  [2] the border walk (0 when min_neighbours == 0)  [3] the numbering and the table.  Copies are not included. */
+int immesh_cloud_clusters_last_timing(immesh_cloud_index* ix, float ms[4]);
 
 #ifdef __cplusplus
 }

@@ -50,7 +50,7 @@ One option looks at the cloud first (include/immesh_align.h), off by default:
                             evaluated by iterated closest-face least squares (immesh_align) from the identity, linearised about the cloud's mean, with
                             point or point-to-plane rows, pairs within D (1.0), at most N iterations (30), and move the cloud by the pose found.  The
                             output gains an `align` block: the options, status, iterations, pose and the rms per iteration
-Two options clean the cloud itself before that (include/immesh_nearest.h, the Outliers rule), off by default:
+Three options clean the cloud itself before that (include/immesh_nearest.h, the Outliers rule and the Clusters rule), off by default:
   --cloud-outliers-knn K MULT | --cloud-outliers-radius R MIN
                             first of all that reads the cloud, before --align: index the cloud, drop the points whose mean distance to their K
                             nearest neighbours within --max-dist exceeds mu + MULT sigma over the cloud (immesh_knn_cloud,
@@ -58,6 +58,12 @@ Two options clean the cloud itself before that (include/immesh_nearest.h, the Ou
                             immesh_cloud_outliers_radius), shrink the index on the device (immesh_cloud_index_apply_outliers) and fetch the kept
                             points (immesh_cloud_index_points), so that accuracy, alignment and completeness see one cloud.  The output gains a
                             `cloud_outliers` block: the arguments, mu, sigma, the threshold and the counts
+  --cloud-clusters R MIN_NB [--cluster-min-points N] [--cluster-keep-largest N]
+                            after the two outlier rules, on the same index: Euclidean clusters of the cloud (immesh_cloud_clusters: DBSCAN with
+                            radius R, a core point has at least MIN_NB others within R; MIN_NB = 0 is plain cluster extraction), then only the
+                            clusters of at least N points and / or the N largest stay (immesh_cloud_clusters_select) and the index shrinks as
+                            above: a small detached object that both outlier rules keep leaves the figures.  The `cloud_outliers` block gains a
+                            `clusters` entry: the arguments, the number of clusters and the counts
 One option compares orientations as well (include/immesh_normals.h), off by default:
   --normals K [--normals-max-dist D] [--normals-min-ratio R] [--viewpoint X Y Z]
                             after the outlier options and --align, behind the distances: a normal per ground-truth point from its K nearest
@@ -78,6 +84,7 @@ evaluate(h, cloud, ...) takes any HotPath whose caster has been built (h.raycast
                               [--remove-self-intersections] [--self-intersections] [--max-candidates N] [--manifold]
                               [--align point|plane [--align-max-dist D] [--align-iters N]]
                               [--cloud-outliers-knn K MULT] [--cloud-outliers-radius R MIN]
+                              [--cloud-clusters R MIN_NB [--cluster-min-points N] [--cluster-keep-largest N]]
                               [--normals K [--normals-max-dist D] [--normals-min-ratio R]]
 """
 import argparse
@@ -267,10 +274,12 @@ def align_cloud(h, cloud, mode, max_dist=1.0, max_iters=30):
                    "rms": hist[:, 1].tolist()}
 
 
-def filter_cloud(h, cloud, knn=None, radius=None, max_dist=1.0):
+def filter_cloud(h, cloud, knn=None, radius=None, max_dist=1.0, clusters=None, cluster_min_points=0, cluster_keep_largest=0):
     """the stray points of a ground-truth cloud taken out on the device, statistical rule first when both are given: knn = (K, MULT) keeps the points
     whose mean distance to their K nearest neighbours (within max_dist) is at most mu + MULT sigma; radius = (R, MIN) keeps the points with at least
-    MIN others within R -> (the kept points as the index holds them, the rules' arguments and counts)"""
+    MIN others within R; clusters = (R, MIN_NB), after the two: DBSCAN with radius R and MIN_NB neighbours for a core point, and only the clusters of
+    at least cluster_min_points points and (cluster_keep_largest > 0) among that many largest stay; noise goes
+    -> (the kept points as the index holds them, the rules' arguments and counts)"""
     cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
     out = {"points_before": len(cloud)}
     h.cloud_index_build(cloud)
@@ -286,7 +295,14 @@ def filter_cloud(h, cloud, knn=None, radius=None, max_dist=1.0):
         st = h.cloud_outliers_radius(min_neighbours)
         h.cloud_index_apply_outliers()
         out["radius"] = {"radius": r, "min_neighbours": min_neighbours, **{n: v for n, v in st.items() if n != "keep"}}
-    kept = h.cloud_index_points()                        # the accuracy half runs on the same cloud as the completeness half
+    if clusters is not None:
+        r, min_neighbours = float(clusters[0]), int(clusters[1])
+        found = h.cloud_clusters(r, min_neighbours, want=())
+        st = h.cloud_clusters_select(min_points=int(cluster_min_points), keep_largest=int(cluster_keep_largest))
+        h.cloud_index_apply_outliers()
+        out["clusters"] = {"radius": r, "min_neighbours": min_neighbours, "min_points": int(cluster_min_points), "keep_largest": int(cluster_keep_largest),
+                           "n_clusters": found["n_clusters"], **found["counts"], **{n: v for n, v in st.items() if n not in ("keep", "not_finite")}}
+    kept = h.cloud_index_points()                       # the accuracy half runs on the same cloud as the completeness half
     out["points_kept"] = len(kept)
     return kept, out
 
@@ -325,6 +341,10 @@ def main():
                     help="drop the cloud points whose mean distance to their K nearest neighbours exceeds mu + MULT sigma, before everything that reads the cloud")
     ap.add_argument("--cloud-outliers-radius", type=float, nargs=2, default=None, metavar=("R", "MIN"),
                     help="drop the cloud points with fewer than MIN others within R, before everything that reads the cloud")
+    ap.add_argument("--cloud-clusters", type=float, nargs=2, default=None, metavar=("R", "MIN_NB"),
+                    help="cluster the cloud (DBSCAN: radius R, a core point has MIN_NB others within R) after the outlier rules and keep the clusters chosen below")
+    ap.add_argument("--cluster-min-points", type=int, default=None, metavar="N", help="with --cloud-clusters: drop the clusters of fewer than N points (0)")
+    ap.add_argument("--cluster-keep-largest", type=int, default=None, metavar="N", help="with --cloud-clusters: keep the N clusters with the most points only (0: all)")
     ap.add_argument("--normals", type=int, default=None, metavar="K", help="add the normal consistency: cloud normals from the K nearest neighbours (2 .. 64)")
     ap.add_argument("--normals-max-dist", type=float, default=None, metavar="D", help="with --normals: neighbours within D (--max-dist)")
     ap.add_argument("--normals-min-ratio", type=float, default=None, metavar="R", help="with --normals: no normal where the middle eigenvalue is not above R times the largest (0)")
@@ -337,6 +357,12 @@ def main():
         ap.error("--cloud-outliers-knn K MULT: K is an integer in 1 .. 64")
     if args.cloud_outliers_radius is not None and not (args.cloud_outliers_radius[1] == int(args.cloud_outliers_radius[1]) and args.cloud_outliers_radius[1] >= 0):
         ap.error("--cloud-outliers-radius R MIN: MIN is an integer, not negative")
+    if args.cloud_clusters is not None and not (args.cloud_clusters[1] == int(args.cloud_clusters[1]) and args.cloud_clusters[1] >= 0):
+        ap.error("--cloud-clusters R MIN_NB: MIN_NB is an integer, not negative")
+    if args.cloud_clusters is None and (args.cluster_min_points is not None or args.cluster_keep_largest is not None):
+        ap.error("--cluster-min-points and --cluster-keep-largest go with --cloud-clusters R MIN_NB")
+    if (args.cluster_min_points or 0) < 0 or (args.cluster_keep_largest or 0) < 0:
+        ap.error("--cluster-min-points N, --cluster-keep-largest N: not negative")
     if args.align is None and (args.align_max_dist is not None or args.align_iters is not None):
         ap.error("--align-max-dist and --align-iters go with --align {point,plane}")
     if args.max_candidates is not None and not (args.remove_self_intersections or args.self_intersections):
@@ -379,8 +405,9 @@ def main():
             extra["topology"] = topology(h)
         if args.self_intersections:
             extra["intersections"] = self_intersections(h, max_candidates)
-        if args.cloud_outliers_knn is not None or args.cloud_outliers_radius is not None:   # the strays leave before the alignment weighs them
-            cloud, extra["cloud_outliers"] = filter_cloud(h, cloud, args.cloud_outliers_knn, args.cloud_outliers_radius, args.max_dist)
+        if args.cloud_outliers_knn is not None or args.cloud_outliers_radius is not None or args.cloud_clusters is not None:   # the strays leave before the alignment weighs them
+            cloud, extra["cloud_outliers"] = filter_cloud(h, cloud, args.cloud_outliers_knn, args.cloud_outliers_radius, args.max_dist, clusters=args.cloud_clusters,
+                                                          cluster_min_points=args.cluster_min_points or 0, cluster_keep_largest=args.cluster_keep_largest or 0)
         if args.align:                                    # the cloud is moved before anything else reads it
             cloud, extra["align"] = align_cloud(h, cloud, args.align, 1.0 if args.align_max_dist is None else args.align_max_dist,
                                                 30 if args.align_iters is None else args.align_iters)
