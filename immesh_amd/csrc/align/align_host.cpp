@@ -21,7 +21,7 @@ bool al_nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
 // the checks a step makes of its options: what it reads
 int al_check_step(immesh_ctx* c, const std::string& who, const immesh_align_options* o) {
     if (!o) { c->err = who + ": options are NULL"; return IMMESH_E_INVAL; }
-    if (!(o->max_dist > 0.0) || !std::isfinite(o->max_dist)) { c->err = who + ": need 0 < max_dist, finite"; return IMMESH_E_INVAL; }
+    if (const int rc = rc_positive(c, who.c_str(), "max_dist", o->max_dist)) return rc;
     if (o->mode != IMMESH_ALIGN_POINT && o->mode != IMMESH_ALIGN_PLANE) { c->err = who + ": mode " + std::to_string(o->mode) + " is neither 0 (POINT) nor 1 (PLANE)"; return IMMESH_E_INVAL; }
     for (int k = 0; k < 3; k++)
         if (!std::isfinite(o->centre[k])) { c->err = who + ": centre is not finite"; return IMMESH_E_INVAL; }
@@ -29,8 +29,7 @@ int al_check_step(immesh_ctx* c, const std::string& who, const immesh_align_opti
 }
 
 int al_check_points(immesh_ctx* c, const std::string& who, const float* pts, int64_t n_pts) {
-    if (n_pts < 0 || n_pts > (int64_t)0x7FFFFFFE || (n_pts > 0 && !pts)) { c->err = who + ": bad point array"; return IMMESH_E_INVAL; }
-    return 0;
+    return rc_points(c, who.c_str(), pts, n_pts);
 }
 
 // the record's events and pinned words, the cloud on the device (queued on the caster's stream)

@@ -22,7 +22,7 @@ namespace {
 
 constexpr int64_t IX_MAX_CANDIDATES = 0x7FFFFFFE;               // the sort's and the scan's int count
 
-int ix_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->ix, b, bytes); }
+int ix_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->ix, b, bytes); }
 
 int ix_passed(immesh_raycaster* r, const char* who) {
     const int rc = rc_built(r, who);
@@ -56,7 +56,7 @@ int immesh_self_intersect(immesh_raycaster* r, int64_t max_candidates, immesh_in
     hipStream_t s = r->s;
     RcIntersect& o = r->ix;
     o.have = false;
-    if ((rc = rc_pass_ready(r, "self_intersect", o, IX_COUNTERS, IX_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "self_intersect", o, IX_COUNTERS, IX_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     if (nf > 0) {
         RcBuf* const per_face[] = {&o.cnt32, &o.off, &o.npart, &o.keep, &o.koff, &o.fmap};
@@ -74,14 +74,14 @@ int immesh_self_intersect(immesh_raycaster* r, int64_t max_candidates, immesh_in
     st = immesh_intersect_stats{};
     st.n_faces = nf; st.n_in_tree = r->tree.n_in;
     // ---- candidates: count, the one round trip for the total, scan, emit
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     ix_launch_take(s, vtx, nv, faces, nf, (int8_t*)o.take.p, cnt);
     ix_launch_walk(s, vtx, faces, nf, take, nodes, r->tree.n_in, cnt32, nullptr, nullptr, cnt);
     if ((rc = ix_read(r, o, 0, 2))) return rc;
     const int64_t n_cand = (int64_t)o.h_cnt[IX_N_CANDIDATES];
     st.n_taking_part = (int64_t)o.h_cnt[IX_N_TAKING]; st.n_candidates = n_cand;
     if (n_cand > max_candidates) {
-        if ((rc = rc_pass_span(r, o, 0, 1, 0))) return rc;
+        if ((rc = rc_pass_span(o, 0, 1, 0))) return rc;
         if (stats) *stats = st;                                 // n_candidates and the counts before it; no result exists
         c->err = "self_intersect: cap " + std::to_string(max_candidates) + " < " + std::to_string(n_cand) + " candidate pairs";
         return IMMESH_E_CAPACITY;
@@ -95,7 +95,7 @@ int immesh_self_intersect(immesh_raycaster* r, int64_t max_candidates, immesh_in
         rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, cnt32, off, nf);
         ix_launch_walk(s, vtx, faces, nf, take, nodes, r->tree.n_in, nullptr, off, (unsigned long long*)o.key.p, cnt);
     }
-    if ((rc = rc_pass_span(r, o, 0, 1, 0))) return rc;
+    if ((rc = rc_pass_span(o, 0, 1, 0))) return rc;
     // ---- tests: the masks, flag / scan / compaction of the hits, the round trip for their number, the sort, the pairs and n_partners
     const int bits = rc_index_bits(nf);
     int64_t n_hits = 0;
@@ -127,7 +127,7 @@ int immesh_self_intersect(immesh_raycaster* r, int64_t max_candidates, immesh_in
         rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, keep, koff, nf);
         ix_launch_map(s, faces, nf, keep, koff, (int32_t*)o.fmap.p, nullptr);
     }
-    if ((rc = rc_pass_end(r, o, 2, 3, 1, 0, IX_COUNTERS))) return rc;
+    if ((rc = rc_pass_end(o, 2, 3, 1, 0, IX_COUNTERS))) return rc;
     const unsigned long long* h = o.h_cnt;
     for (int k = 0; k < 4; k++) st.n_share[k] = (int64_t)h[IX_N_SHARE0 + k];
     st.n_pairs = (int64_t)h[IX_N_PAIRS]; st.n_pairs_share0 = (int64_t)h[IX_N_PAIRS_SHARE0]; st.n_pairs_share1 = (int64_t)h[IX_N_PAIRS_SHARE1];
@@ -179,7 +179,7 @@ int immesh_self_intersect_apply(immesh_raycaster* r) {
         rc_swap(r->faces, o.faces_out);
     }
     if ((rc = rc_build(r, r->n_vtx, n_kept))) return rc;        // discards what read the snapshot, this pass too; the stream is idle on return
-    return rc_pass_span(r, o, 4, 5, 2);
+    return rc_pass_span(o, 4, 5, 2);
 }
 
 int immesh_self_intersect_last_timing(immesh_raycaster* r, float* ms) {

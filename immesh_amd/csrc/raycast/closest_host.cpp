@@ -19,12 +19,11 @@ int rc_dist_copy(immesh_ctx* c, const RcDist& q, int64_t n_q, double* d2_out, fl
 
 int rc_dist_reduce(immesh_ctx* c, const char* who, const char* grow_who, const char* none, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, float* ms,
                    RcDist& q, double bin_width, int32_t n_bins, immesh_closest_stats* stats, int64_t* hist_out) {
-    const std::string w(who);
-    if (!(bin_width > 0.0) || !std::isfinite(bin_width)) { c->err = w + ": need 0 < bin_width, finite"; return IMMESH_E_INVAL; }
-    if (n_bins < 1 || n_bins > (1 << 20)) { c->err = w + ": n_bins " + std::to_string(n_bins) + " outside [1, 2^20]"; return IMMESH_E_INVAL; }
-    if (!q.have) { c->err = w + ": " + none; return IMMESH_E_INVAL; }
-    (void)hipSetDevice(c->cfg.device);
     int rc;
+    if ((rc = rc_positive(c, who, "bin_width", bin_width))) return rc;
+    if (n_bins < 1 || n_bins > (1 << 20)) { c->err = std::string(who) + ": n_bins " + std::to_string(n_bins) + " outside [1, 2^20]"; return IMMESH_E_INVAL; }
+    if ((rc = rc_have(c, who, q.have, none))) return rc;
+    (void)hipSetDevice(c->cfg.device);
     const int64_t blocks = dq_stats_blocks(q.n);
     const size_t hist_bytes = ((size_t)n_bins + 1) * 8;
     if ((rc = rc_grow(c, grow_who, q.part, (size_t)blocks * sizeof(DqStatsDev)))) return rc;
@@ -35,11 +34,7 @@ int rc_dist_reduce(immesh_ctx* c, const char* who, const char* grow_who, const c
     HIPCHK(c, hipMemsetAsync(q.hist.p, 0, hist_bytes, s));
     dq_launch_stats(s, (const float*)q.dist.p, (const uint8_t*)q.status.p, q.n, bw, n_bins, (DqStatsDev*)q.part.p, (unsigned long long*)q.hist.p,
                     (DqStatsDev*)q.res.p);
-    HIPCHK(c, hipEventRecord(ev1, s));
-    HIPCHK(c, hipMemcpyAsync(q.h_res, q.res.p, sizeof(DqStatsDev), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(ms, ev0, ev1);
+    if ((rc = rc_span_end(c, s, ev0, ev1, ms, q.h_res, q.res.p, sizeof(DqStatsDev)))) return rc;
     int64_t overflow = 0;
     HIPCHK(c, hipMemcpy(&overflow, (const char*)q.hist.p + (size_t)n_bins * 8, 8, hipMemcpyDeviceToHost));
     if (hist_out) HIPCHK(c, hipMemcpy(hist_out, q.hist.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost));
@@ -82,8 +77,7 @@ int immesh_closest_points(immesh_raycaster* r, const immesh_ray_frame* frame, co
     RcDist& q = cl.q;
     int rc;
     if ((rc = rc_built(r, "closest_points"))) return rc;
-    if (n_pts < 0 || n_pts > (int64_t)0x7FFFFFFE || (n_pts > 0 && !pts)) { c->err = "closest_points: bad point array"; return IMMESH_E_INVAL; }
-    if (!(max_dist > 0.0) || !std::isfinite(max_dist)) { c->err = "closest_points: need 0 < max_dist, finite"; return IMMESH_E_INVAL; }
+    if ((rc = rc_points(c, "closest_points", pts, n_pts)) || (rc = rc_positive(c, "closest_points", "max_dist", max_dist))) return rc;
     RcFrame fr = {};
     if (frame && (rc = rc_frame(c, "closest_points", frame, &fr))) return rc;
     (void)hipSetDevice(c->cfg.device);
@@ -104,10 +98,7 @@ int immesh_closest_points(immesh_raycaster* r, const immesh_ray_frame* frame, co
     rc_launch_closest(s, fr, frame != nullptr, (const float*)cl.pts.p, n_pts, r2, (const float*)r->vtx.p, (const int32_t*)r->faces.p,
                       (const RcNode*)r->tree.nodes.p, r->tree.n_in, (double*)q.d2.p, (float*)q.dist.p, (int32_t*)q.id.p, (float*)q.xyz.p, (int8_t*)cl.side.p,
                       (uint8_t*)q.status.p);
-    HIPCHK(c, hipEventRecord(cl.ev[1], s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&cl.ms[0], cl.ev[0], cl.ev[1]);
+    if ((rc = rc_span_end(c, s, cl.ev[0], cl.ev[1], &cl.ms[0]))) return rc;
     if ((rc = rc_dist_copy(c, q, n_pts, d2_out, dist_out, face_out, xyz_out))) return rc;
     if (side_out && n_pts > 0) HIPCHK(c, hipMemcpy(side_out, cl.side.p, n, hipMemcpyDeviceToHost));
     q.n = n_pts;

@@ -13,41 +13,9 @@
 
 namespace {
 
-constexpr int64_t CL_MAX_ARG = (int64_t)0x7FFFFFFE;
-
-int cl_built(immesh_cloud_index* x, const char* who) {
-    if (!x->built) { x->ctx->err = std::string(who) + ": no index has been built (immesh_cloud_index_build)"; return IMMESH_E_INVAL; }
-    return 0;
-}
-
 int cl_have(immesh_cloud_index* x, const char* who) {
-    int rc;
-    if ((rc = cl_built(x, who))) return rc;
-    if (!x->cl.have) { x->ctx->err = std::string(who) + ": no immesh_cloud_clusters call since the index's last build or apply"; return IMMESH_E_INVAL; }
-    return 0;
-}
-
-int cl_check_count(immesh_cloud_index* x, const char* who, const char* what, int64_t v) {
-    if (v < 0 || v > CL_MAX_ARG) { x->ctx->err = std::string(who) + ": need " + what + " in [0, 2^31 - 2]"; return IMMESH_E_INVAL; }
-    return 0;
-}
-
-int cl_grow(immesh_cloud_index* x, RcBuf& b, size_t bytes) { return rc_grow(x->ctx, "cloud_index", b, bytes); }
-
-// the events, the pinned words and the device counters, at the first call
-int cl_ready(immesh_cloud_index* x) {
-    immesh_ctx* c = x->ctx;
-    (void)hipSetDevice(c->cfg.device);
-    for (hipEvent_t& e : x->cl.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!x->cl.h_cnt) HIPCHK(c, hipHostMalloc((void**)&x->cl.h_cnt, CL_PINNED * 8));
-    return cl_grow(x, x->cl.dcnt, CL_COUNTERS * 8);
-}
-
-float cl_span(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
+    const int rc = cx_built(x, who);
+    return rc ? rc : rc_have(x->ctx, who, x->cl.have, "no immesh_cloud_clusters call since the index's last build or apply");
 }
 
 }  // namespace
@@ -60,32 +28,32 @@ int immesh_cloud_clusters(immesh_cloud_index* x, double radius, int64_t min_neig
     immesh_ctx* c = x->ctx;
     RcClusters& q = x->cl;
     int rc;
-    if ((rc = cl_built(x, "cloud_clusters"))) return rc;
-    if (!(radius > 0.0) || !std::isfinite(radius)) { c->err = "cloud_clusters: need 0 < radius, finite"; return IMMESH_E_INVAL; }
-    if ((rc = cl_check_count(x, "cloud_clusters", "min_neighbours", min_neighbours))) return rc;
-    if ((rc = cl_ready(x))) return rc;
+    if ((rc = cx_built(x, "cloud_clusters"))) return rc;
+    if ((rc = rc_positive(c, "cloud_clusters", "radius", radius))) return rc;
+    if ((rc = rc_count_arg(c, "cloud_clusters", "min_neighbours", min_neighbours))) return rc;
+    if ((rc = cx_ready(x, q, CL_COUNTERS, CL_PINNED))) return rc;
     hipStream_t s = x->s;
     q.have = false;
     const int64_t n = x->n_pts, n_in = x->tree.n_in;
     const size_t m = (size_t)n;
     const bool counted = min_neighbours > 0;
-    if (counted && ((rc = cl_grow(x, q.cnt, m * 4)) || (rc = cl_grow(x, q.status, m)))) return rc;
-    if ((rc = cl_grow(x, q.core, m)) || (rc = cl_grow(x, q.kind, m))) return rc;
-    if ((rc = cl_grow(x, q.parent, m * 4)) || (rc = cl_grow(x, q.root, m * 4)) || (rc = cl_grow(x, q.flag, m * 4))) return rc;
-    if ((rc = cl_grow(x, q.num, m * 4)) || (rc = cl_grow(x, q.label, m * 4))) return rc;
-    if ((rc = cl_grow(x, x->tree.temp, rd_scan_temp_bytes(1, 1, std::max<int64_t>(n, 1)) + 256))) return rc;
+    if (counted && ((rc = rc_pass_grow(q, q.count, m * 4)) || (rc = rc_pass_grow(q, q.status, m)))) return rc;
+    if ((rc = rc_pass_grow(q, q.core, m)) || (rc = rc_pass_grow(q, q.kind, m))) return rc;
+    if ((rc = rc_pass_grow(q, q.parent, m * 4)) || (rc = rc_pass_grow(q, q.root, m * 4)) || (rc = rc_pass_grow(q, q.flag, m * 4))) return rc;
+    if ((rc = rc_pass_grow(q, q.num, m * 4)) || (rc = rc_pass_grow(q, q.label, m * 4))) return rc;
+    if ((rc = rc_pass_grow(q, x->tree.temp, rd_scan_temp_bytes(1, 1, std::max<int64_t>(n, 1)) + 256))) return rc;
     const float* cloud = (const float*)x->pts.p;
     const RcNode* nodes = (const RcNode*)x->tree.nodes.p;
     const double r2 = radius * radius;
     uint8_t *core = (uint8_t*)q.core.p, *kind = (uint8_t*)q.kind.p;
     int32_t *parent = (int32_t*)q.parent.p, *root = (int32_t*)q.root.p, *flag = (int32_t*)q.flag.p, *num = (int32_t*)q.num.p;
-    unsigned long long* cnt = (unsigned long long*)q.dcnt.p;
+    unsigned long long* cnt = (unsigned long long*)q.cnt.p;
     unsigned long long* h = q.h_cnt;
     HIPCHK(c, hipMemsetAsync(cnt, 0, CL_COUNTERS * 8, s));
     // the count (its buffers are the clusters' own: the index's last Count query stays) and the kinds
     HIPCHK(c, hipEventRecord(q.ev[0], s));
-    if (counted) kn_launch_count(s, RcFrame{}, 2, cloud, n, r2, cloud, nodes, n_in, (int32_t*)q.cnt.p, (uint8_t*)q.status.p);
-    cl_launch_kind(s, cloud, n, counted ? (const int32_t*)q.cnt.p : nullptr, (int32_t)min_neighbours, core, kind, parent, root);
+    if (counted) kn_launch_count(s, RcFrame{}, 2, cloud, n, r2, cloud, nodes, n_in, (int32_t*)q.count.p, (uint8_t*)q.status.p);
+    cl_launch_kind(s, cloud, n, counted ? (const int32_t*)q.count.p : nullptr, (int32_t)min_neighbours, core, kind, parent, root);
     HIPCHK(c, hipEventRecord(q.ev[1], s));
     // the joins
     HIPCHK(c, hipEventRecord(q.ev[2], s));
@@ -104,35 +72,30 @@ int immesh_cloud_clusters(immesh_cloud_index* x, double radius, int64_t min_neig
         HIPCHK(c, hipMemcpyAsync(&h[5], num + (n - 1), 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(&h[6], flag + (n - 1), 4, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(c, hipEventRecord(q.ev[7], s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = rc_pass_end(q, 5, 7, 3, 0, 0))) return rc;
+    const float scan_ms = q.ms[3];
     const int64_t n_clusters = (int64_t)h[5] + (int64_t)h[6];
     const size_t nc = (size_t)n_clusters;
-    if ((rc = cl_grow(x, q.first, nc * 4)) || (rc = cl_grow(x, q.npts, nc * 4)) || (rc = cl_grow(x, q.ncore, nc * 4))) return rc;
-    if ((rc = cl_grow(x, q.boxkey, nc * 24)) || (rc = cl_grow(x, q.box, nc * 24))) return rc;
+    if ((rc = rc_pass_grow(q, q.first, nc * 4)) || (rc = rc_pass_grow(q, q.npts, nc * 4)) || (rc = rc_pass_grow(q, q.ncore, nc * 4))) return rc;
+    if ((rc = rc_pass_grow(q, q.boxkey, nc * 24)) || (rc = rc_pass_grow(q, q.box, nc * 24))) return rc;
     // the table
     HIPCHK(c, hipEventRecord(q.ev[8], s));
     cl_launch_preset(s, n_clusters, (int32_t*)q.first.p, (int32_t*)q.npts.p, (int32_t*)q.ncore.p, (uint32_t*)q.boxkey.p);
     cl_launch_table(s, cloud, n, kind, root, num, n_clusters, (int32_t*)q.label.p, (int32_t*)q.first.p, (int32_t*)q.npts.p, (int32_t*)q.ncore.p,
                     (uint32_t*)q.boxkey.p, cnt);
     cl_launch_unkey(s, n_clusters, (const uint32_t*)q.boxkey.p, (float*)q.box.p);
-    HIPCHK(c, hipEventRecord(q.ev[9], s));
-    HIPCHK(c, hipMemcpyAsync(h, cnt, CL_COUNTERS * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    q.ms[0] = cl_span(q.ev[0], q.ev[1]);
-    q.ms[1] = cl_span(q.ev[2], q.ev[3]);
-    q.ms[2] = counted ? cl_span(q.ev[4], q.ev[5]) : 0.0f;
-    q.ms[3] = (cl_span(q.ev[6], q.ev[4]) + cl_span(q.ev[5], q.ev[7])) + cl_span(q.ev[8], q.ev[9]);   // the flatten, the scan, the table
+    if ((rc = rc_pass_end(q, 8, 9, 3, 0, CL_COUNTERS))) return rc;
+    q.ms[0] = rc_pass_ms(q, 0, 1);
+    q.ms[1] = rc_pass_ms(q, 2, 3);
+    q.ms[2] = counted ? rc_pass_ms(q, 4, 5) : 0.0f;
+    q.ms[3] = (rc_pass_ms(q, 6, 4) + scan_ms) + q.ms[3];   // the flatten, the scan, the table
     if (h[CL_ERROR]) {
         c->err = "cloud_clusters: a union did not finish within its step bound (a defect of the library)";
         return IMMESH_E_INTERNAL;
     }
     q.n_clusters = n_clusters;
     q.have = true;
-    if (counts)
-        for (int i = 0; i < 4; i++) counts[i] = (int64_t)h[i];
+    rc_pass_counts(q, counts);
     if (n_clusters_out) *n_clusters_out = n_clusters;
     if ((rc = rc_fetch(c, label_out, q.label.p, m * 4))) return rc;
     return rc_fetch(c, kind_out, q.kind.p, m);
@@ -161,19 +124,14 @@ int immesh_cloud_clusters_select(immesh_cloud_index* x, int64_t min_points, int6
     if (!x) return IMMESH_E_INVAL;
     immesh_ctx* c = x->ctx;
     RcClusters& q = x->cl;
-    RcKnn& k = x->kn;
     int rc;
     if ((rc = cl_have(x, "cloud_clusters_select"))) return rc;
-    if ((rc = cl_check_count(x, "cloud_clusters_select", "min_points", min_points))) return rc;
-    if ((rc = cl_check_count(x, "cloud_clusters_select", "max_points", max_points))) return rc;
-    if ((rc = cl_check_count(x, "cloud_clusters_select", "keep_largest", keep_largest))) return rc;
+    if ((rc = rc_count_arg(c, "cloud_clusters_select", "min_points", min_points))) return rc;
+    if ((rc = rc_count_arg(c, "cloud_clusters_select", "max_points", max_points))) return rc;
+    if ((rc = rc_count_arg(c, "cloud_clusters_select", "keep_largest", keep_largest))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = x->s;
     const int64_t n = x->n_pts, nc = q.n_clusters;
-    // the mask is the index's last mask: its events, buffers and pinned counts are those of the Outliers rules (knn_host.cpp)
-    for (hipEvent_t& e : k.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (!k.h_cnt) HIPCHK(c, hipHostMalloc((void**)&k.h_cnt, 4 * 8));
     // the Select rule per cluster: host code over n_points, read back once
     q.h_npts.resize((size_t)nc);
     q.h_keepc.resize((size_t)nc);
@@ -189,26 +147,13 @@ int immesh_cloud_clusters_select(immesh_cloud_index* x, int64_t min_points, int6
         std::sort(q.h_rank.begin(), q.h_rank.end(), [np](int32_t a, int32_t b) { return np[a] != np[b] ? np[a] > np[b] : a < b; });
         for (int64_t r = keep_largest; r < nc; r++) q.h_keepc[(size_t)q.h_rank[(size_t)r]] = 0;
     }
-    k.have_mask = false;
-    if ((rc = cl_grow(x, q.keepc, (size_t)nc * 4))) return rc;
-    if ((rc = cl_grow(x, k.flag, (size_t)n * 4))) return rc;
-    if ((rc = cl_grow(x, k.keep8, (size_t)n))) return rc;
-    if ((rc = cl_grow(x, k.mcnt, 4 * 8))) return rc;
-    unsigned long long* cnt = (unsigned long long*)k.mcnt.p;
+    if ((rc = rc_pass_grow(q, q.keepc, (size_t)nc * 4))) return rc;
     if (nc > 0) HIPCHK(c, hipMemcpyAsync(q.keepc.p, q.h_keepc.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(k.ev[2], s));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, 4 * 8, s));
-    cl_launch_mask(s, n, (const uint8_t*)q.kind.p, (const int32_t*)q.label.p, (const int32_t*)q.keepc.p, nc, keep_noise, (int32_t*)k.flag.p, (uint8_t*)k.keep8.p, cnt);
-    HIPCHK(c, hipEventRecord(k.ev[3], s));
-    HIPCHK(c, hipMemcpyAsync(k.h_cnt, cnt, 4 * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&k.ms[1], k.ev[2], k.ev[3]);
-    k.n_kept = (int64_t)k.h_cnt[0];
-    k.have_mask = true;
-    if (counts)
-        for (int i = 0; i < 4; i++) counts[i] = (int64_t)k.h_cnt[i];
-    return rc_fetch(c, keep_out, k.keep8.p, (size_t)n);
+    // the mask is the index's last mask, as the Outliers rules' is (knn_host.cpp)
+    CxMask m;
+    if ((rc = cx_mask_begin(x, &m))) return rc;
+    cl_launch_mask(s, n, (const uint8_t*)q.kind.p, (const int32_t*)q.label.p, (const int32_t*)q.keepc.p, nc, keep_noise, m.flag, m.keep8, m.cnt);
+    return cx_mask_end(x, counts, keep_out);
 }
 
 int immesh_cloud_clusters_last_timing(immesh_cloud_index* x, float ms[4]) {

@@ -13,13 +13,10 @@
 namespace {
 
 constexpr int64_t CN_MAX_POINTS = (int64_t)1 << RC_INDEX_BITS;
-constexpr int64_t CN_MAX_QUERY = (int64_t)0x7FFFFFFE;
 
 int cn_check_query(immesh_cloud_index* x, const char* who, double max_dist) {
-    immesh_ctx* c = x->ctx;
-    if (!x->built) { c->err = std::string(who) + ": no index has been built (immesh_cloud_index_build)"; return IMMESH_E_INVAL; }
-    if (!(max_dist > 0.0) || !std::isfinite(max_dist)) { c->err = std::string(who) + ": need 0 < max_dist, finite"; return IMMESH_E_INVAL; }
-    return 0;
+    const int rc = cx_built(x, who);
+    return rc ? rc : rc_positive(x->ctx, who, "max_dist", max_dist);
 }
 
 int cn_grow_results(immesh_cloud_index* x, size_t n) {
@@ -33,15 +30,11 @@ int cn_grow_results(immesh_cloud_index* x, size_t n) {
     return rc_grow(c, "cloud_index", q.status, n);
 }
 
-// behind the traversal launch: the end event, the wait, the copies
+// behind the traversal launch: the end of the query's span, the copies
 int cn_finish_query(immesh_cloud_index* x, int64_t n_q, double* d2_out, float* dist_out, int32_t* index_out, float* xyz_out) {
-    immesh_ctx* c = x->ctx;
-    HIPCHK(c, hipEventRecord(x->ev[3], x->s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(x->s));
-    (void)hipEventElapsedTime(&x->ms[1], x->ev[2], x->ev[3]);
-    const int rc = rc_dist_copy(c, x->q, n_q, d2_out, dist_out, index_out, xyz_out);
-    if (rc) return rc;
+    int rc;
+    if ((rc = rc_span_end(x->ctx, x->s, x->ev[2], x->ev[3], &x->ms[1]))) return rc;
+    if ((rc = rc_dist_copy(x->ctx, x->q, n_q, d2_out, dist_out, index_out, xyz_out))) return rc;
     x->q.n = n_q;
     x->q.have = true;
     return 0;
@@ -93,14 +86,12 @@ int immesh_cloud_index_build(immesh_cloud_index* x, const float* xyz, int64_t n_
     if (!x) return IMMESH_E_INVAL;
     immesh_ctx* c = x->ctx;
     // before anything is touched: a refused cloud leaves the built index as it was
-    if (n_pts < 0 || n_pts > CN_MAX_QUERY || (n_pts > 0 && !xyz)) { c->err = "cloud_index_build: bad point array"; return IMMESH_E_INVAL; }
+    int rc;
+    if ((rc = rc_points(c, "cloud_index_build", xyz, n_pts))) return rc;
     if (n_pts > CN_MAX_POINTS) { c->err = "cloud_index_build: more than 2^30 points"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
-    x->built = false; x->q.have = false;
-    x->kn.changed();   // neighbour results and masks belong to the cloud they were made on
-    x->nr.changed();   // and so do the normals
-    x->cl.changed();   // and the clusters
-    int rc;
+    x->built = false;
+    cx_cloud_changed(x);   // every derived result belongs to the cloud it was made on
     if ((rc = rc_grow(c, "cloud_index", x->pts, (size_t)n_pts * 12))) return rc;
     if (n_pts > 0) HIPCHK(c, hipMemcpyAsync(x->pts.p, xyz, (size_t)n_pts * 12, hipMemcpyHostToDevice, x->s));
     const RcLeaves src = {(const float*)x->pts.p, n_pts, nullptr};
@@ -126,7 +117,7 @@ int immesh_nearest_points(immesh_cloud_index* x, const immesh_ray_frame* frame, 
     immesh_ctx* c = x->ctx;
     int rc;
     if ((rc = cn_check_query(x, "nearest_points", max_dist))) return rc;
-    if (n_q < 0 || n_q > CN_MAX_QUERY || (n_q > 0 && !pts)) { c->err = "nearest_points: bad point array"; return IMMESH_E_INVAL; }
+    if ((rc = rc_points(c, "nearest_points", pts, n_q))) return rc;
     RcFrame fr = {};
     if (frame && (rc = rc_frame(c, "nearest_points", frame, &fr))) return rc;
     (void)hipSetDevice(c->cfg.device);
@@ -147,11 +138,8 @@ int immesh_nearest_samples(immesh_cloud_index* x, immesh_raycaster* r, double ma
     if (!x) return IMMESH_E_INVAL;
     immesh_ctx* c = x->ctx;
     int rc;
-    if (!r) { c->err = "nearest_samples: no caster"; return IMMESH_E_INVAL; }
-    if (r->ctx != c) { c->err = "nearest_samples: the caster and the index belong to different contexts"; return IMMESH_E_INVAL; }
-    if ((rc = cn_check_query(x, "nearest_samples", max_dist))) return rc;
-    if (!r->built) { c->err = "nearest_samples: no hierarchy has been built on the caster"; return IMMESH_E_INVAL; }
-    if (!r->sm.have) { c->err = "nearest_samples: no samples since the caster's last build (immesh_mesh_sample)"; return IMMESH_E_INVAL; }
+    if ((rc = cx_caster(x, r, "nearest_samples")) || (rc = cn_check_query(x, "nearest_samples", max_dist)) || (rc = cx_caster_built(x, r, "nearest_samples", true)))
+        return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = x->s;
     x->q.have = false;
@@ -184,7 +172,7 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
     RcSample& q = r->sm;
     int rc;
     if ((rc = rc_built(r, "mesh_sample"))) return rc;
-    if (!(density > 0.0) || !std::isfinite(density)) { c->err = "mesh_sample: need 0 < density, finite"; return IMMESH_E_INVAL; }
+    if ((rc = rc_positive(c, "mesh_sample", "density", density))) return rc;
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     q.have = false; q.n = 0;
@@ -197,13 +185,9 @@ int immesh_mesh_sample(immesh_raycaster* r, double density, uint64_t seed, float
     HIPCHK(c, hipEventRecord(q.ev[0], s));
     HIPCHK(c, hipMemsetAsync(q.total.p, 0, 8, s));
     ms_launch_count(s, (const float*)r->vtx.p, r->n_vtx, (const int32_t*)r->faces.p, nf, density, seed, (int32_t*)q.cnt.p, (unsigned long long*)q.total.p);
-    HIPCHK(c, hipEventRecord(q.ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(q.h_total, q.total.p, 8, hipMemcpyDeviceToHost, s));     // the one count the host needs: it sizes the samples
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&q.ms[0], q.ev[0], q.ev[1]);
+    if ((rc = rc_span_end(c, s, q.ev[0], q.ev[1], &q.ms[0], q.h_total, q.total.p, 8))) return rc;   // the one count the host needs: it sizes the samples
     const int64_t total = q.h_total[0];
-    if (total < 0 || total > CN_MAX_QUERY) {
+    if (total < 0 || total > RC_MAX_COUNT) {
         c->err = "mesh_sample: too many samples (" + std::to_string(total) + " > 2^31 - 2)";
         return IMMESH_E_CAPACITY;
     }

@@ -186,19 +186,23 @@ struct RcSample {
     }
 };
 
-// What the seven passes over the snapshot share (analysis, orientation, holes, manifold, simplification, smoothing, self-intersections): the events of their spans, the device
-// counters and their pinned copy, all created by rc_pass_ready at the pass' first call and never before; `have`: a result of the current snapshot (of
-// the current analysis, for the orientation, the holes and the manifold pass) exists.  rc_snapshot_changed / rc_analysis_changed below clear it.
+// What the seven passes over the snapshot share (analysis, orientation, holes, manifold, simplification, smoothing, self-intersections), and the three
+// rules of the cloud index (neighbours, normals, clusters): the events of their spans, the device counters and their pinned copy, all created by
+// rc_pass_ready at the pass' first call and never before, on the owner's context and stream; `have`: a result of the current snapshot (of the current
+// analysis, for the orientation, the holes and the manifold pass; of the index's current cloud) exists.  rc_snapshot_changed / rc_analysis_changed and
+// cx_cloud_changed / cx_normals_changed below clear it.
 struct RcPass {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of up to three spans
+    hipEvent_t ev[10] = {};                                    // begin / end of up to five spans (the clusters call has five)
     unsigned long long* h_cnt = nullptr;                       // pinned: the counters, and what the pass asks for behind them
     RcBuf cnt;                                                 // n_cnt int64 (the pass' header names them)
+    immesh_ctx* ctx = nullptr;                                 // the owner's context and stream
+    hipStream_t s = nullptr;
     const char* who = "";                                      // the prefix of the pass' rc_grow messages
     int n_cnt = 0;
     bool have = false;
-    float ms[3] = {0.0f, 0.0f, 0.0f};                          // the spans' device time
+    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};                    // the spans' device time, as the pass reports it
     ~RcPass() {
-        rc_destroy_events(ev, 6);
+        rc_destroy_events(ev, 10);
         if (h_cnt) (void)hipHostFree(h_cnt);
     }
 };
@@ -321,14 +325,27 @@ void rc_analysis_changed(immesh_raycaster* r);
 int rc_built(immesh_raycaster* r, const char* who);
 int rc_analysed(immesh_raycaster* r, const char* who);
 int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none);
-// A pass on the caster's stream.  ready: the events and n_pinned pinned words if absent, the n_cnt device counters; `who` prefixes the messages of
-// this and every later rc_pass_grow.  begin: ev[e0] recorded, the counters zeroed.  end: ev[e1] recorded, the counters [first, first + n) copied to
-// h_cnt, the launches' error checked, the stream idle, ms[span] = e0 .. e1.  span: an end without counters (an apply).
-int rc_pass_ready(immesh_raycaster* r, const char* who, RcPass& p, int n_cnt, int n_pinned);
-int rc_pass_grow(immesh_raycaster* r, const RcPass& p, RcBuf& b, size_t bytes);
-int rc_pass_begin(immesh_raycaster* r, RcPass& p, int e0);
-int rc_pass_end(immesh_raycaster* r, RcPass& p, int e0, int e1, int span, int first, int n);
-int rc_pass_span(immesh_raycaster* r, RcPass& p, int e0, int e1, int span);
+// the argument checks more than one entry point makes, each refusal with the caller's name in front: "<who>: <none>" unless `have`; "<who>: need 0 <
+// <what>, finite"; "<who>: bad point array" (n outside [0, RC_MAX_COUNT], or points without an array); "<who>: need <what> in [0, 2^31 - 2]"
+constexpr int64_t RC_MAX_COUNT = (int64_t)0x7FFFFFFE;
+int rc_have(immesh_ctx* c, const char* who, bool have, const char* none);
+int rc_positive(immesh_ctx* c, const char* who, const char* what, double v);
+int rc_points(immesh_ctx* c, const char* who, const float* pts, int64_t n);
+int rc_count_arg(immesh_ctx* c, const char* who, const char* what, int64_t v);
+// The end of a span on s: ev1 recorded, `bytes` of device memory copied to the pinned dst behind it (nothing when bytes == 0), the launches' error
+// checked, s idle, *ms = ev0 .. ev1.
+int rc_span_end(immesh_ctx* c, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, float* ms, void* dst = nullptr, const void* src = nullptr, size_t bytes = 0);
+// A pass on its owner's stream.  ready: the events and n_pinned pinned words if absent, the n_cnt device counters; the pass remembers c, s and `who`,
+// which prefixes the messages of this and every later rc_pass_grow.  begin: ev[e0] recorded, the counters zeroed.  end: rc_span_end over ev[e0],
+// ev[e1] and ms[span] with the counters [first, first + n) copied to h_cnt (n == 0: no copy).  span: an end without counters or error check (an
+// apply).  ms: e0 .. e1 of recorded events.  counts: h_cnt[0 .. 3] to a caller's array that may be NULL.
+int rc_pass_ready(immesh_ctx* c, hipStream_t s, const char* who, RcPass& p, int n_cnt, int n_pinned);
+int rc_pass_grow(const RcPass& p, RcBuf& b, size_t bytes);
+int rc_pass_begin(RcPass& p, int e0);
+int rc_pass_end(RcPass& p, int e0, int e1, int span, int first, int n);
+int rc_pass_span(RcPass& p, int e0, int e1, int span);
+float rc_pass_ms(const RcPass& p, int e0, int e1);
+void rc_pass_counts(const RcPass& p, int64_t counts[4]);
 
 // closest face of every point (closest_kernels.hip) --------------------------------------------------------------------------------------------
 // status[i]: 0 a face, 1 no face within max_dist, 2 the point is not finite.  has_frame == 0: the points are world coordinates.
@@ -343,68 +360,41 @@ void dq_launch_stats(hipStream_t s, const float* dist, const uint8_t* status, in
 
 // ---- mesh-to-cloud distances (include/immesh_nearest.h): nearest_host.cpp owns the index and the sampler's host side ---------------------------------
 // k nearest neighbours, radius counts, the outlier masks and their apply on a cloud index (knn_host.cpp): allocated at the first call of one of
-// them, never before.  A build and an apply clear the three flags.
-struct RcKnn {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // traversal, mask, apply: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the mask's four counts
+// them, never before.  Its three flags stand for RcPass' one.
+struct RcKnn : RcPass {                                        // spans: traversal, mask, apply; counters: the last mask's four counts
     RcBuf pts;                                                 // the last point-mode query's points
-    RcBuf cnt, idx, d2;                                        // the last Neighbours query of either mode: counts, and the lists when asked for
+    RcBuf count, idx, d2;                                      // the last Neighbours query of either mode: counts, and the lists when asked for
     RcBuf mean, status;                                        // the last cloud-mode Neighbours query (the statistical rule reads them)
     RcBuf rcnt, rstatus;                                       // the last cloud-mode Count query (the radius rule reads them)
     RcBuf pstatus;                                             // a point-mode query's status (nothing reads it afterwards)
-    RcBuf flag, keep8, off, mcnt;                              // the last mask as int32 and uint8, its scan, its four device counts
+    RcBuf flag, keep8, off;                                    // the last mask as int32 and uint8 (cx_mask_begin / cx_mask_end), its scan
     RcBuf out, kept;                                           // the apply: out changes places with the index's cloud; kept: the old indices
     std::vector<double> h_mean;                                // the statistical rule's one read-back
     bool have_knn = false, have_count = false, have_mask = false;
     int64_t n_kept = 0;
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    void changed() { have_knn = have_count = have_mask = false; }
-    ~RcKnn() {
-        rc_destroy_events(ev, 6);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
 };
 
 // the Euclidean clusters of the index's cloud (include/immesh_nearest.h, the Clusters rule; clusters_host.cpp): allocated at the first
-// immesh_cloud_clusters, never before.  Its counts are its own: the index's last Count query stays as it is.  A build and an apply drop the clusters.
+// immesh_cloud_clusters, never before.  Its counts are its own: the index's last Count query stays as it is.
 constexpr int CL_ERROR = 4, CL_COUNTERS = 5, CL_PINNED = 8;   // device words: the four counts, the error flag; pinned: those, and [5], [6] the scan's total in two halves
-struct RcClusters {
-    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count, joins, border walk, numbering, table: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: CL_PINNED words
-    RcBuf cnt, status;                                        // the Count launch's outputs
+struct RcClusters : RcPass {                                   // events: count, joins, border walk, numbering, table; spans: count, joins, border walk, the rest
+    RcBuf count, status;                                       // the Count launch's outputs
     RcBuf core, kind;                                          // per point, uint8: the kind before the border walk (0 core, 2 finite and not core, 3 not finite), and after
     RcBuf parent, root, flag, num, label;                      // per point, int32: the union-find, the class' root (-1: none), root == self, its scan, the number
     RcBuf first, npts, ncore, boxkey, box;                     // per cluster: the table (boxkey: six order-preserving keys, box: their floats)
-    RcBuf dcnt, keepc;                                         // CL_COUNTERS device words; a select's per-cluster keep (int32)
+    RcBuf keepc;                                               // a select's per-cluster keep (int32)
     std::vector<int32_t> h_npts, h_keepc, h_rank;              // a select's one read-back, its answer, the ranking
-    bool have = false;
     int64_t n_clusters = 0;
-    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    void changed() { have = false; }
-    ~RcClusters() {
-        rc_destroy_events(ev, 10);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
 };
 
 // the normals of the index's cloud and their agreement with a caster's face normals (include/immesh_normals.h; normals_host.cpp): allocated at the
-// first call of one of them, never before.  A build and an apply drop the normals and with them the agreement.
-struct RcNormals {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // normals, agreement, reduction: begin / end
-    unsigned long long* h_cnt = nullptr;                       // pinned: the four counts of the last launch
+// first call of one of them, never before.
+struct RcNormals : RcPass {                                    // spans: normals, agreement, reduction; counters: the four counts of the last launch
     RcBuf normal, status;                                      // the last normals: 3 floats and a uint8 per cloud point (the agreement reads them)
-    RcBuf curv, eig, cnt;                                      // the last normals call's other outputs
-    RcBuf dcnt;                                                // the four device counts
+    RcBuf curv, eig, count;                                    // the last normals call's other outputs
     RcBuf agree, face;                                         // the last agreement: s as a float; the cloud direction's closest face
     RcDist a;                                                  // the last agreement as the reduction reads it: dist = |s|, status 0 a pair / 1 none / 2 not finite
-    bool have = false;
     int64_t n = 0;                                             // the cloud's size when the normals were made
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    void changed() { have = false; a.have = false; }
-    ~RcNormals() {
-        rc_destroy_events(ev, 6);
-        if (h_cnt) (void)hipHostFree(h_cnt);
-    }
 };
 
 // An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi, built by the same rc_tree_build, one point per leaf.
@@ -426,6 +416,25 @@ struct immesh_cloud_index {
     RcNormals nr;
     RcClusters cl;
 };
+// the index's discard rule (its table stands above them in raycast_host.cpp): what was made on the cloud, and what read the normals
+void cx_cloud_changed(immesh_cloud_index* x);
+void cx_normals_changed(immesh_cloud_index* x);
+// the state an entry point needs: an index has been built; r is a caster of the index's context; it has a hierarchy and, when asked, samples
+int cx_built(immesh_cloud_index* x, const char* who);
+int cx_caster(immesh_cloud_index* x, const immesh_raycaster* r, const char* who);
+int cx_caster_built(immesh_cloud_index* x, const immesh_raycaster* r, const char* who, bool sampled);
+// rc_pass_ready for a rule of the index, on the index's stream with "cloud_index" in front of its messages
+int cx_ready(immesh_cloud_index* x, RcPass& p, int n_cnt, int n_pinned);
+// The index's last mask (knn_host.cpp): the two outlier rules and the clusters' select each launch their kernel between the two, writing *m.  begin:
+// the record ready, the old mask gone, the buffers grown, the mask span begun with the four counts zeroed.  end: the span ended, n_kept and the mask
+// valid, counts[] and keep_out (either may be NULL) filled.
+struct CxMask {
+    int32_t* flag;                                             // keep_i as the apply's scan reads it
+    uint8_t* keep8;                                            // keep_i as it is fetched
+    unsigned long long* cnt;                                   // the rule's four counts
+};
+int cx_mask_begin(immesh_cloud_index* x, CxMask* m);
+int cx_mask_end(immesh_cloud_index* x, int64_t counts[4], uint8_t* keep_out);
 
 // nearest cloud point of every query; status[i] as rc_launch_closest writes it (0 a neighbour, 1 none within max_dist, 2 the query is not finite), so
 // dq_launch_stats reduces it.  n_in == 0 reads no node.  has_frame == 0: pts are world floats (the host's points, or the sampler's on the device).

@@ -66,43 +66,90 @@ int rc_analysed(immesh_raycaster* r, const char* who) {
     return 0;
 }
 
-int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none) {
-    if (!p.have) { r->ctx->err = std::string(who) + ": " + none; return IMMESH_E_INVAL; }
+int rc_have(immesh_ctx* c, const char* who, bool have, const char* none) {
+    if (!have) { c->err = std::string(who) + ": " + none; return IMMESH_E_INVAL; }
     return 0;
 }
 
-int rc_pass_ready(immesh_raycaster* r, const char* who, RcPass& p, int n_cnt, int n_pinned) {
-    immesh_ctx* c = r->ctx;
+int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none) { return rc_have(r->ctx, who, p.have, none); }
+
+int rc_positive(immesh_ctx* c, const char* who, const char* what, double v) {
+    if (!(v > 0.0) || !std::isfinite(v)) { c->err = std::string(who) + ": need 0 < " + what + ", finite"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_points(immesh_ctx* c, const char* who, const float* pts, int64_t n) {
+    if (n < 0 || n > RC_MAX_COUNT || (n > 0 && !pts)) { c->err = std::string(who) + ": bad point array"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_count_arg(immesh_ctx* c, const char* who, const char* what, int64_t v) {
+    if (v < 0 || v > RC_MAX_COUNT) { c->err = std::string(who) + ": need " + what + " in [0, 2^31 - 2]"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int cx_built(immesh_cloud_index* x, const char* who) { return rc_have(x->ctx, who, x->built, "no index has been built (immesh_cloud_index_build)"); }
+
+int cx_caster(immesh_cloud_index* x, const immesh_raycaster* r, const char* who) {
+    const int rc = rc_have(x->ctx, who, r != nullptr, "no caster");
+    return rc ? rc : rc_have(x->ctx, who, r->ctx == x->ctx, "the caster and the index belong to different contexts");
+}
+
+int cx_caster_built(immesh_cloud_index* x, const immesh_raycaster* r, const char* who, bool sampled) {
+    const int rc = rc_have(x->ctx, who, r->built, "no hierarchy has been built on the caster");
+    return rc || !sampled ? rc : rc_have(x->ctx, who, r->sm.have, "no samples since the caster's last build (immesh_mesh_sample)");
+}
+
+int rc_span_end(immesh_ctx* c, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, float* ms, void* dst, const void* src, size_t bytes) {
+    HIPCHK(c, hipEventRecord(ev1, s));
+    if (bytes > 0) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));   // the read-back
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(ms, ev0, ev1);
+    return 0;
+}
+
+int rc_pass_ready(immesh_ctx* c, hipStream_t s, const char* who, RcPass& p, int n_cnt, int n_pinned) {
     for (hipEvent_t& e : p.ev)
         if (!e) HIPCHK(c, hipEventCreate(&e));
     if (!p.h_cnt) HIPCHK(c, hipHostMalloc((void**)&p.h_cnt, (size_t)n_pinned * 8));
-    p.who = who; p.n_cnt = n_cnt;
-    return rc_pass_grow(r, p, p.cnt, (size_t)n_cnt * 8);
+    p.ctx = c; p.s = s; p.who = who; p.n_cnt = n_cnt;
+    return rc_pass_grow(p, p.cnt, (size_t)n_cnt * 8);
 }
 
-int rc_pass_grow(immesh_raycaster* r, const RcPass& p, RcBuf& b, size_t bytes) { return rc_grow(r->ctx, p.who, b, bytes); }
+int cx_ready(immesh_cloud_index* x, RcPass& p, int n_cnt, int n_pinned) {
+    (void)hipSetDevice(x->ctx->cfg.device);
+    return rc_pass_ready(x->ctx, x->s, "cloud_index", p, n_cnt, n_pinned);
+}
 
-int rc_pass_begin(immesh_raycaster* r, RcPass& p, int e0) {
-    HIPCHK(r->ctx, hipEventRecord(p.ev[e0], r->s));
-    HIPCHK(r->ctx, hipMemsetAsync(p.cnt.p, 0, (size_t)p.n_cnt * 8, r->s));
+int rc_pass_grow(const RcPass& p, RcBuf& b, size_t bytes) { return rc_grow(p.ctx, p.who, b, bytes); }
+
+int rc_pass_begin(RcPass& p, int e0) {
+    HIPCHK(p.ctx, hipEventRecord(p.ev[e0], p.s));
+    HIPCHK(p.ctx, hipMemsetAsync(p.cnt.p, 0, (size_t)p.n_cnt * 8, p.s));
     return 0;
 }
 
-int rc_pass_end(immesh_raycaster* r, RcPass& p, int e0, int e1, int span, int first, int n) {
-    immesh_ctx* c = r->ctx;
-    HIPCHK(c, hipEventRecord(p.ev[e1], r->s));
-    HIPCHK(c, hipMemcpyAsync(p.h_cnt + first, (const unsigned long long*)p.cnt.p + first, (size_t)n * 8, hipMemcpyDeviceToHost, r->s));   // the read-back
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(r->s));
+int rc_pass_end(RcPass& p, int e0, int e1, int span, int first, int n) {
+    return rc_span_end(p.ctx, p.s, p.ev[e0], p.ev[e1], &p.ms[span], p.h_cnt + first, (const unsigned long long*)p.cnt.p + first, (size_t)n * 8);
+}
+
+int rc_pass_span(RcPass& p, int e0, int e1, int span) {
+    HIPCHK(p.ctx, hipEventRecord(p.ev[e1], p.s));
+    HIPCHK(p.ctx, hipStreamSynchronize(p.s));
     (void)hipEventElapsedTime(&p.ms[span], p.ev[e0], p.ev[e1]);
     return 0;
 }
 
-int rc_pass_span(immesh_raycaster* r, RcPass& p, int e0, int e1, int span) {
-    HIPCHK(r->ctx, hipEventRecord(p.ev[e1], r->s));
-    HIPCHK(r->ctx, hipStreamSynchronize(r->s));
-    (void)hipEventElapsedTime(&p.ms[span], p.ev[e0], p.ev[e1]);
-    return 0;
+float rc_pass_ms(const RcPass& p, int e0, int e1) {
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, p.ev[e0], p.ev[e1]);
+    return ms;
+}
+
+void rc_pass_counts(const RcPass& p, int64_t counts[4]) {
+    if (counts)
+        for (int i = 0; i < 4; i++) counts[i] = (int64_t)p.h_cnt[i];
 }
 
 int rc_tree_build(immesh_ctx* c, const char* who, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int64_t* h_count, RcTree& t, int64_t n, const RcLeaves& src) {
@@ -208,6 +255,33 @@ void rc_snapshot_changed(immesh_raycaster* r) {
     r->sp.have = false;
     r->so.have = false;
     r->ix.have = false;
+}
+
+// What a change of a cloud index's state discards.  A change of the cloud is immesh_cloud_index_build or immesh_cloud_index_apply_outliers; new
+// normals are an immesh_cloud_normals call.
+//
+//   derived result                              | the cloud changes     | new normals
+//   the last nearest query (q)                   | discarded             | stays
+//   the last cloud-mode Neighbours query (kn)    | discarded             | stays
+//   the last cloud-mode Count query (kn)         | discarded             | stays
+//   the last mask (kn)                           | discarded             | stays
+//   the normals (nr)                             | discarded             | replaced
+//   the agreement (nr.a)                         | discarded             | discarded (it read the normals)
+//   the clusters (cl)                            | discarded             | stay
+//
+// A producer clears its own flag when it starts: a point-mode query has none and discards nothing, a clusters call counts into buffers of its own and
+// leaves the Count query, and the three producers of a mask share cx_mask_begin.  A new rule on the index adds one line to one of these two functions
+// and nowhere else.
+void cx_normals_changed(immesh_cloud_index* x) {
+    x->nr.a.have = false;   // an agreement belongs to the normals it read
+}
+
+void cx_cloud_changed(immesh_cloud_index* x) {
+    x->q.have = false;
+    x->kn.have_knn = x->kn.have_count = x->kn.have_mask = false;
+    x->nr.have = false;
+    cx_normals_changed(x);
+    x->cl.have = false;
 }
 
 // the hierarchy over r->vtx / r->faces (already on the device, queued on the caster's stream)
@@ -330,10 +404,7 @@ int immesh_raycast(immesh_raycaster* r, const immesh_ray_frame* frame, const flo
     HIPCHK(c, hipEventRecord(r->ev[2], s));
     rc_launch_cast(s, fr, (const float*)r->dirs[m].p, origins ? (const float*)r->org[m].p : nullptr, n_rays, t_min, t_max, mode, (const float*)r->vtx.p,
                    (const int32_t*)r->faces.p, (const RcNode*)r->tree.nodes.p, r->tree.n_in, (float*)r->t[m].p, (int32_t*)r->face[m].p);
-    HIPCHK(c, hipEventRecord(r->ev[3], s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&r->ms[1], r->ev[2], r->ev[3]);
+    if ((rc = rc_span_end(c, s, r->ev[2], r->ev[3], &r->ms[1]))) return rc;
     if (t_out && n_rays > 0) HIPCHK(c, hipMemcpy(t_out, r->t[m].p, (size_t)n_rays * 4, hipMemcpyDeviceToHost));
     if (face_out && n_rays > 0) HIPCHK(c, hipMemcpy(face_out, r->face[m].p, (size_t)n_rays * 4, hipMemcpyDeviceToHost));
     if (m == 0) { r->have_cast = true; r->have_origins = origins != nullptr; r->n_rays = n_rays; r->frame = fr; }
@@ -381,12 +452,8 @@ int immesh_raycast_points(immesh_raycaster* r, double downsample_res, float* xyz
         }
         rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, keep, (int32_t*)r->koff.p, n);
         rd_launch_compact(s, n, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
-        HIPCHK(c, hipEventRecord(r->ev[5], s));
-        HIPCHK(c, hipMemcpyAsync(r->h_small + 1, r->small.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(s));
+        if ((rc = rc_span_end(c, s, r->ev[4], r->ev[5], &r->ms[2], r->h_small + 1, r->small.p, 8))) return rc;
         r->n_points = r->h_small[1];
-        (void)hipEventElapsedTime(&r->ms[2], r->ev[4], r->ev[5]);
     }
     if (n_out) *n_out = r->n_points;
     if (!xyz_out || r->n_points == 0) return 0;

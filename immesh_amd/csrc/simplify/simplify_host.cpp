@@ -23,7 +23,7 @@ namespace {
 
 constexpr int64_t SP_MAX_VTX = 0x7FFFFFFE;                      // the sort's and the scan's int count
 
-int sp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->sp, b, bytes); }
+int sp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->sp, b, bytes); }
 
 int sp_passed(immesh_raycaster* r, const char* who) {
     const int rc = rc_built(r, who);
@@ -47,7 +47,7 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
     hipStream_t s = r->s;
     RcSimplify& o = r->sp;
     o.have = false;
-    if ((rc = rc_pass_ready(r, "simplify", o, SP_COUNTERS, SP_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "simplify", o, SP_COUNTERS, SP_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     const bool work = nf > 0 && nv > 0;
     if (work) {
@@ -70,7 +70,7 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
         const size_t temp = std::max({exclusive_sum_temp_bytes((int)ns), sort_pairs_u64_temp_bytes((int)ns), sort_pairs_u32_temp_bytes((int)ns)}) + 256;
         if ((rc = sp_grow(r, r->tree.temp, temp))) return rc;  // the caster's scan and sort scratch
     }
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     if (work) {
         const float* vtx = (const float*)r->vtx.p;
         const int32_t* faces = (const int32_t*)r->faces.p;
@@ -122,7 +122,7 @@ int immesh_simplify(immesh_raycaster* r, double cell, int32_t mode, int32_t merg
         exclusive_sum_i32(s, temp, temp_bytes, keep, koff, (int)nf);
         sp_launch_compact(s, faces, nf, vmap, keep, koff, (int32_t*)o.faces_out.p, (int32_t*)o.fmap.p, cnt);
     }
-    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, SP_COUNTERS))) return rc;   // the one read-back
+    if ((rc = rc_pass_end(o, 0, 1, 0, 0, SP_COUNTERS))) return rc;   // the one read-back
     const unsigned long long* h = o.h_cnt;
     immesh_simplify_stats& st = o.st;
     st.n_vertices_in = nv; st.n_vertices_used = (int64_t)h[SP_N_USED]; st.n_alone_not_finite = (int64_t)h[SP_N_ALONE_NOT_FINITE];
@@ -194,7 +194,7 @@ int immesh_simplify_apply(immesh_raycaster* r) {
         rc_swap(r->faces, o.faces_out);
     }
     if ((rc = rc_build(r, nv, nf))) return rc;                  // discards what read the snapshot, this pass too; the stream is idle on return
-    return rc_pass_span(r, o, 2, 3, 1);
+    return rc_pass_span(o, 2, 3, 1);
 }
 
 int immesh_simplify_last_timing(immesh_raycaster* r, float* ms) {

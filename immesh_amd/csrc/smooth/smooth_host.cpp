@@ -24,7 +24,7 @@ namespace {
 
 constexpr int64_t SM_MAX_COUNT = 0x7FFFFFFE;                    // the sort's and the scan's int count
 
-int sm_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->so, b, bytes); }
+int sm_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->so, b, bytes); }
 
 int sm_sizes(immesh_raycaster* r, const char* who) {
     if (6 * r->n_faces > SM_MAX_COUNT) { r->ctx->err = std::string(who) + ": more than 2^31 - 2 directed pairs (6 x " + std::to_string(r->n_faces) + " faces)"; return IMMESH_E_INVAL; }
@@ -61,7 +61,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
     hipStream_t s = r->s;
     RcSmooth& o = r->so;
     o.have = false;
-    if ((rc = rc_pass_ready(r, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     const bool ring = nf > 0 && nv > 0;
     if (nv > 0) {
@@ -82,7 +82,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         if ((rc = sm_grow(r, r->tree.temp, temp))) return rc;   // the caster's scan and sort scratch
     }
     const float* vtx = (const float*)r->vtx.p;
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     if (nv > 0) {
         HIPCHK(c, hipMemsetAsync(o.flag.p, 0, (size_t)nv * SM_FLAGS, s));
         if (!ring) {                                            // no face: every vertex is unused and every row empty
@@ -123,7 +123,7 @@ int immesh_smooth(immesh_raycaster* r, int32_t n_steps, double lambda, double mu
         }
         sm_launch_finish(s, vtx, (const float*)o.pos[o.cur].p, nv, (const int8_t*)o.flag.p, cnt);
     }
-    if ((rc = rc_pass_end(r, o, 2, 3, 1, 0, SM_COUNTERS))) return rc;   // the one read-back; it ends both spans
+    if ((rc = rc_pass_end(o, 2, 3, 1, 0, SM_COUNTERS))) return rc;   // the one read-back; it ends both spans
     (void)hipEventElapsedTime(&o.ms[0], o.ev[0], o.ev[1]);
     const unsigned long long* h = o.h_cnt;
     immesh_smooth_stats& st = o.st;
@@ -178,7 +178,7 @@ int immesh_smooth_apply(immesh_raycaster* r) {
         rc_swap(r->vtx, o.pos[o.cur]);                          // the stream is idle: the pass synchronised
     }
     if ((rc = rc_build(r, nv, nf))) return rc;                  // discards what read the snapshot, this pass too; the stream is idle on return
-    return rc_pass_span(r, o, 4, 5, 2);
+    return rc_pass_span(o, 4, 5, 2);
 }
 
 int immesh_smooth_last_timing(immesh_raycaster* r, float* ms) {
@@ -199,7 +199,7 @@ int immesh_vertex_normals(immesh_raycaster* r, float* normals_out, int64_t* n_ze
     (void)hipSetDevice(c->cfg.device);
     hipStream_t s = r->s;
     RcSmooth& o = r->so;
-    if ((rc = rc_pass_ready(r, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "smooth", o, SM_COUNTERS, SM_COUNTERS))) return rc;
     if ((rc = sm_grow(r, o.normals, (size_t)nv * 12))) return rc;
     if (nf > 0) {
         RcBuf* const per_corner[] = {&o.nkey_a, &o.nkey_b, &o.nval_a, &o.nval_b};

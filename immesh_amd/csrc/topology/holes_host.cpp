@@ -26,7 +26,7 @@ constexpr int64_t HL_MAX_VTX = 0x7FFFFFFF;                      // the scan's in
 constexpr int64_t HL_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;   // what a build takes
 constexpr int64_t HL_MAX_ANALYSED = ((int64_t)0x7FFFFFFE) / 3;  // what an analysis takes
 
-int hl_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->hl, b, bytes); }
+int hl_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->hl, b, bytes); }
 
 int hl_passed(immesh_raycaster* r, const char* who) {
     const int rc = rc_analysed(r, who);
@@ -51,7 +51,7 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
     RcHoles& o = r->hl;
     const int64_t nv = r->n_vtx, n_half = q.n_half, n_loops = q.st.n_boundary_loops, n_room = q.st.n_boundary, largest = q.st.largest_loop_edges;
     o.have = false;
-    if ((rc = rc_pass_ready(r, "topology_holes", o, HC_COUNTERS, HC_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "topology_holes", o, HC_COUNTERS, HC_COUNTERS))) return rc;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     if (n_loops > 0) {
         if ((rc = hl_grow(r, o.vt, (size_t)nv * HV_TABLES * 4))) return rc;
@@ -66,7 +66,7 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
         if ((rc = hl_grow(r, o.new_loop, (size_t)n_room * 4))) return rc;
         if ((rc = hl_grow(r, r->tree.temp, exclusive_sum_temp_bytes((int)std::max(nv, n_loops)) + 256))) return rc;   // the caster's scan scratch
     }
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     if (n_loops > 0) {
         const unsigned long long* key = (const unsigned long long*)q.key_b.p;
         int32_t *vt = (int32_t*)o.vt.p, *lt = (int32_t*)o.lt.p, *cycle = (int32_t*)o.cycle.p, *cloop = (int32_t*)o.cloop.p;
@@ -89,7 +89,7 @@ int immesh_topology_holes(immesh_raycaster* r, int64_t max_edges, double max_dia
         exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, lt + HL_FILL * n_loops, lt + HL_FOFF * n_loops, (int)n_loops);
         hl_launch_emit(s, n_room, cycle, cloop, lt, n_loops, (int32_t*)o.new_faces.p, (int32_t*)o.new_loop.p, cnt);
     }
-    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, HC_COUNTERS))) return rc;   // the one read-back
+    if ((rc = rc_pass_end(o, 0, 1, 0, 0, HC_COUNTERS))) return rc;   // the one read-back
     const unsigned long long* h = o.h_cnt;
     immesh_holes_stats& st = o.st;
     st.n_loops = n_loops; st.n_simple = (int64_t)h[HC_N_SIMPLE]; st.n_nonsimple = (int64_t)h[HC_N_NONSIMPLE];
@@ -165,7 +165,7 @@ int immesh_topology_holes_apply(immesh_raycaster* r) {
     if (n_new > 0) HIPCHK(c, hipMemcpyAsync((int32_t*)o.merged.p + 3 * nf, o.new_faces.p, (size_t)n_new * 12, hipMemcpyDeviceToDevice, s));
     rc_swap(r->faces, o.merged);                                // the stream runs in order: the copies are queued before the build reads them
     if ((rc = rc_build(r, r->n_vtx, total))) return rc;         // discards what read the snapshot, this pass too; the stream is idle on return
-    return rc_pass_span(r, o, 2, 3, 1);
+    return rc_pass_span(o, 2, 3, 1);
 }
 
 int immesh_topology_holes_last_timing(immesh_raycaster* r, float* ms) {

@@ -22,7 +22,7 @@ namespace {
 
 constexpr int64_t MF_MAX_VTX = 0x7FFFFFFF;                      // an index is an int32
 
-int mf_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->mf, b, bytes); }
+int mf_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->mf, b, bytes); }
 
 int mf_passed(immesh_raycaster* r, const char* who) {
     const int rc = rc_analysed(r, who);
@@ -44,7 +44,7 @@ int immesh_topology_manifold(immesh_raycaster* r, immesh_manifold_stats* stats) 
     RcManifold& o = r->mf;
     const int64_t nf = r->n_faces, nv = r->n_vtx, n3 = 3 * nf, n_half = q.n_half, n_used = q.st.n_vertices_used;   // (3 n_faces <= 2^31 - 2: the analysis)
     o.have = false;
-    if ((rc = rc_pass_ready(r, "topology_manifold", o, MF_COUNTERS, MF_COUNTERS + 2))) return rc;
+    if ((rc = rc_pass_ready(c, s, "topology_manifold", o, MF_COUNTERS, MF_COUNTERS + 2))) return rc;
     RcBuf* const per_corner[] = {&o.parent, &o.root, &o.isroot, &o.off, &o.ncnt, &o.nlnk, &o.fanof, &o.faces_out, &o.fan_out};
     for (RcBuf* b : per_corner)
         if ((rc = mf_grow(r, *b, (size_t)n3 * 4))) return rc;
@@ -57,7 +57,7 @@ int immesh_topology_manifold(immesh_raycaster* r, immesh_manifold_stats* stats) 
     int32_t *ncnt = (int32_t*)o.ncnt.p, *nlnk = (int32_t*)o.nlnk.p, *fanof = (int32_t*)o.fanof.p;
     unsigned long long* cnt = (unsigned long long*)o.cnt.p;
     unsigned long long* h = o.h_cnt;
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     int64_t n_fans = 0;
     if (n_half > 0) {
         mf_launch_init(s, n3, parent, ncnt, nlnk);
@@ -104,7 +104,7 @@ int immesh_topology_manifold(immesh_raycaster* r, immesh_manifold_stats* stats) 
         mf_launch_vertices(s, n_used, start, fv, n_fans, nv, (int32_t*)o.nfans.p, cnt);
     }
     mf_launch_emit(s, faces, nf, flag, root, fanof, (const int32_t*)o.ft.p, n_fans, (int32_t*)o.faces_out.p, (int32_t*)o.fan_out.p, cnt);
-    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, MF_COUNTERS))) return rc;
+    if ((rc = rc_pass_end(o, 0, 1, 0, 0, MF_COUNTERS))) return rc;
     if (h[MF_ERROR]) {
         c->err = "topology_manifold: a union did not finish within its step bound (a defect of the library)";
         return IMMESH_E_INTERNAL;
@@ -188,7 +188,7 @@ int immesh_topology_manifold_apply(immesh_raycaster* r) {
     if (total > 0) rc_swap(r->vtx, o.vtx_out);                  // the stream is idle: the pass synchronised
     if (nf > 0) rc_swap(r->faces, o.faces_out);
     if ((rc = rc_build(r, total, nf))) return rc;               // discards what read the snapshot, this pass too; the stream is idle on return
-    return rc_pass_span(r, o, 2, 3, 1);
+    return rc_pass_span(o, 2, 3, 1);
 }
 
 int immesh_topology_manifold_last_timing(immesh_raycaster* r, float* ms) {

@@ -18,7 +18,7 @@ static_assert(sizeof(immesh_orient_stats) == 9 * 8 && offsetof(immesh_orient_sta
 
 namespace {
 
-int ot_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->ot, b, bytes); }
+int ot_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->ot, b, bytes); }
 
 int ot_oriented(immesh_raycaster* r, const char* who) {
     const int rc = rc_analysed(r, who);
@@ -52,7 +52,7 @@ int immesh_topology_orient(immesh_raycaster* r, int32_t mode, const double* view
     RcOrient& o = r->ot;
     const int64_t nf = r->n_faces, n_bound = q.n_counting, n_half = q.n_half;
     o.have = false;
-    if ((rc = rc_pass_ready(r, "topology_orient", o, OT_COUNTERS, OT_COUNTERS))) return rc;
+    if ((rc = rc_pass_ready(c, s, "topology_orient", o, OT_COUNTERS, OT_COUNTERS))) return rc;
     if ((rc = ot_grow(r, o.cover, (size_t)nf * 8))) return rc;
     if ((rc = ot_grow(r, o.label, (size_t)nf * 4))) return rc;
     if ((rc = ot_grow(r, o.base, (size_t)nf))) return rc;
@@ -68,7 +68,7 @@ int immesh_topology_orient(immesh_raycaster* r, int32_t mode, const double* view
     int32_t *cover = (int32_t*)o.cover.p, *label = (int32_t*)o.label.p, *root = (int32_t*)o.root.p, *num = (int32_t*)o.num.p, *patch = (int32_t*)o.patch.p;
     int32_t* tab = (int32_t*)o.tab.p;
     int8_t* base = (int8_t*)o.base.p;
-    if ((rc = rc_pass_begin(r, o, 0))) return rc;
+    if ((rc = rc_pass_begin(o, 0))) return rc;
     if (nf > 0) {
         if (n_bound > 0) HIPCHK(c, hipMemsetAsync(tab, 0, (size_t)n_bound * OT_TABLES * 4, s));
         ot_launch_init(s, 2 * nf, cover);
@@ -81,7 +81,7 @@ int immesh_topology_orient(immesh_raycaster* r, int32_t mode, const double* view
         ot_launch_decide(s, n_bound, mode, tab, cnt);
         ot_launch_flip(s, faces, nf, patch, base, tab, n_bound, (int8_t*)o.flip.p, (int32_t*)o.out.p);
     }
-    if ((rc = rc_pass_end(r, o, 0, 1, 0, 0, OT_COUNTERS))) return rc;   // the one read-back
+    if ((rc = rc_pass_end(o, 0, 1, 0, 0, OT_COUNTERS))) return rc;   // the one read-back
     const unsigned long long* h = o.h_cnt;
     if (h[OT_ERROR]) {
         c->err = "topology_orient: a union did not finish within its step bound (a defect of the library)";
@@ -141,7 +141,7 @@ int immesh_topology_orient_apply(immesh_raycaster* r) {
     RcOrient& o = r->ot;
     HIPCHK(c, hipEventRecord(o.ev[2], s));
     if (r->n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, o.out.p, (size_t)r->n_faces * 12, hipMemcpyDeviceToDevice, s));
-    if ((rc = rc_pass_span(r, o, 2, 3, 1))) return rc;
+    if ((rc = rc_pass_span(o, 2, 3, 1))) return rc;
     // what a successful build discards, and the hierarchy stays.  Nothing else the caster keeps depends on the order of a face's vertices: the
     // hierarchy holds boxes and face indices, and the closest-point results of the last query stay readable after a build too.
     rc_snapshot_changed(r);

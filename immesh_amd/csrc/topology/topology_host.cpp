@@ -23,7 +23,7 @@ namespace {
 
 constexpr int64_t TP_MAX_FACES = ((int64_t)0x7FFFFFFE) / 3;   // 3 n_faces <= 2^31 - 2: the sort's int count, the half-edge id
 
-int tp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r, r->tp, b, bytes); }
+int tp_grow(immesh_raycaster* r, RcBuf& b, size_t bytes) { return rc_pass_grow(r->tp, b, bytes); }
 
 // scan and sort scratch: the caster's (the reinforce pass and the sampler share it too)
 int tp_temp(immesh_raycaster* r, int64_t n_scan, int64_t n_sort) {
@@ -54,7 +54,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
     hipStream_t s = r->s;
     q.have = false;
     rc_analysis_changed(r);
-    if ((rc = rc_pass_ready(r, "topology", q, TP_COUNTERS, TP_COUNTERS + 2))) return rc;
+    if ((rc = rc_pass_ready(c, s, "topology", q, TP_COUNTERS, TP_COUNTERS + 2))) return rc;
     if ((rc = tp_grow(r, q.flag, (size_t)nf * 4))) return rc;
     if ((rc = tp_grow(r, q.off, (size_t)nf * 4))) return rc;
     if ((rc = tp_grow(r, q.parent, (size_t)nf * 4))) return rc;
@@ -70,7 +70,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
     int32_t *flag = (int32_t*)q.flag.p, *off = (int32_t*)q.off.p, *parent = (int32_t*)q.parent.p, *vparent = (int32_t*)q.vparent.p;
     unsigned long long* cnt = (unsigned long long*)q.cnt.p;
     unsigned long long* h = q.h_cnt;
-    if ((rc = rc_pass_begin(r, q, 0))) return rc;
+    if ((rc = rc_pass_begin(q, 0))) return rc;
     int64_t n_counting = 0;
     if (nf > 0) {
         if (nv > 0) HIPCHK(c, hipMemsetAsync(q.used.p, 0, (size_t)nv * 4, s));
@@ -112,7 +112,7 @@ int immesh_topology_analyse(immesh_raycaster* r, immesh_topology_stats* stats) {
             tp_launch_largest(s, root, num, (const int32_t*)q.nfaces.p, nf, cnt);
         }
     }
-    if ((rc = rc_pass_end(r, q, 0, 1, 0, 0, TP_COUNTERS))) return rc;
+    if ((rc = rc_pass_end(q, 0, 1, 0, 0, TP_COUNTERS))) return rc;
     if (h[TP_ERROR]) {
         c->err = "topology_analyse: a union did not finish within its step bound (a defect of the library)";
         return IMMESH_E_INTERNAL;
@@ -236,7 +236,7 @@ int immesh_topology_select(immesh_raycaster* r, int64_t min_faces, double min_di
         exclusive_sum_i32(s, r->tree.temp.p, r->tree.temp.bytes, (const int32_t*)q.keep32.p, (int32_t*)q.koff.p, (int)nf);
         tp_launch_compact(s, (const int32_t*)r->faces.p, (const int32_t*)q.keep32.p, (const int32_t*)q.koff.p, nf, (int32_t*)q.out.p,
                           (unsigned long long*)q.cnt.p);
-        if ((rc = rc_pass_end(r, q, 2, 3, 1, TP_N_KEPT, 1))) return rc;
+        if ((rc = rc_pass_end(q, 2, 3, 1, TP_N_KEPT, 1))) return rc;
         kept = (int64_t)q.h_cnt[TP_N_KEPT];
         if ((rc = rc_fetch(c, keep_out, q.keep8.p, (size_t)nf))) return rc;
     }
