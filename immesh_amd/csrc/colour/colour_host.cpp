@@ -8,12 +8,8 @@
 #include <vector>
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_colour.h"
+#include "../raycast/rc_host.hpp"
 #include "colour.hpp"
-
-struct ClBuf {   // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 
 struct immesh_colourer {
     immesh_ctx* ctx = nullptr;
@@ -23,7 +19,7 @@ struct immesh_colourer {
     void* st_block = nullptr;                 // the state arrays, one allocation
     immesh_colour_stats* h_stats = nullptr;   // pinned (immesh_ctx::pinned)
     char* h_stage = nullptr; size_t h_stage_bytes = 0;   // pinned staging: the frame, an id list
-    ClBuf img, ids, flags, off, cand, cell, depth, sel, uv, tab, temp, partials, small, fetch;
+    RcBuf img, ids, flags, off, cand, cell, depth, sel, uv, tab, temp, partials, small, fetch;
     int64_t n_sel = 0;                        // render set of the last image
     bool sel_identity = false;                // ... it is 0 .. n_sel - 1 (set ALL without selection: no list was written)
     const int32_t* d_sel = nullptr;
@@ -31,21 +27,6 @@ struct immesh_colourer {
 };
 
 namespace {
-
-int cl_grow(immesh_colourer* r, ClBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return 0;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        r->ctx->err = "colour: hipMalloc(" + std::to_string(want) + " B) failed";
-        return IMMESH_E_NOMEM;
-    }
-    b.bytes = want;
-    return 0;
-}
 
 // The frame's staging buffer grows with the image size and is freed with the colourer, so it is a pinned allocation of the colourer's own:
 // immesh_ctx::pinned (host_ctx.hpp) hands out fixed-size blocks that live until immesh_destroy -- right for the 64-byte statistics block, not for this.
@@ -76,10 +57,8 @@ int cl_check_image(immesh_ctx* c, const immesh_image* im, int32_t model, int32_t
     if (im->row_stride_bytes < 3 * (int64_t)im->cols) return cl_inval(c, "row_stride_bytes " + std::to_string(im->row_stride_bytes) + " is below 3 * cols");
     for (double v : {im->fx, im->fy, im->cx, im->cy})
         if (!std::isfinite(v)) return cl_inval(c, "intrinsics are not finite");
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(im->rot[i])) return cl_inval(c, "camera rotation is not finite");
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(im->pos[i])) return cl_inval(c, "camera position is not finite");
+    const int rc = rc_finite_pose(c, "colour", "camera", im->rot, im->pos);
+    if (rc) return rc;
     if (!(im->fov_margin >= 0.0) || !(im->fov_margin < 0.5)) return cl_inval(c, "fov_margin must be in [0, 0.5)");
     if (!(im->inv_exposure > 0.0) || !std::isfinite(im->inv_exposure)) return cl_inval(c, "inv_exposure must be finite and > 0");
     for (double v : {im->obs_time, im->min_depth, im->max_depth, im->max_pe_error})
@@ -140,15 +119,11 @@ void immesh_colourer_destroy(immesh_colourer* r) {
     if (!r) return;
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
-    for (ClBuf* b : {&r->img, &r->ids, &r->flags, &r->off, &r->cand, &r->cell, &r->depth, &r->sel, &r->uv, &r->tab, &r->temp, &r->partials, &r->small,
-                     &r->fetch})
-        if (b->p) (void)hipFree(b->p);
     if (r->st_block) (void)hipFree(r->st_block);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
+    rc_destroy_events(r->ev, 4);
     if (r->h_stage) (void)hipHostFree(r->h_stage);
     if (r->s) (void)hipStreamDestroy(r->s);
-    delete r;   // (h_stats belongs to the context's pinned blocks)
+    delete r;   // the members release their buffers (h_stats belongs to the context's pinned blocks)
 }
 
 int immesh_colour_image(immesh_colourer* r, const immesh_image* im, int32_t model, int32_t set, const int32_t* ids, int64_t n_ids, double md,
@@ -200,22 +175,22 @@ int immesh_colour_image(immesh_colourer* r, const immesh_image* im, int32_t mode
     const int n_blocks = std::max(1, cl_update_blocks(n_bound));
     const size_t nb = (size_t)std::max(n_bound, 1);
     if ((rc = cl_grow_stage(r, img_bytes + ids_bytes))) return rc;
-    if ((rc = cl_grow(r, r->img, img_bytes))) return rc;
-    if ((rc = cl_grow(r, r->small, sizeof(ClCounters) + sizeof(immesh_colour_stats)))) return rc;
-    if ((rc = cl_grow(r, r->uv, nb * 8))) return rc;
-    if ((rc = cl_grow(r, r->partials, (size_t)n_blocks * 8))) return rc;
-    if (ids_bytes && (rc = cl_grow(r, r->ids, ids_bytes))) return rc;
+    if ((rc = rc_grow(c, "colour", r->img, img_bytes))) return rc;
+    if ((rc = rc_grow(c, "colour", r->small, sizeof(ClCounters) + sizeof(immesh_colour_stats)))) return rc;
+    if ((rc = rc_grow(c, "colour", r->uv, nb * 8))) return rc;
+    if ((rc = rc_grow(c, "colour", r->partials, (size_t)n_blocks * 8))) return rc;
+    if (ids_bytes && (rc = rc_grow(c, "colour", r->ids, ids_bytes))) return rc;
     if (recent || select) {
-        if ((rc = cl_grow(r, r->flags, nb * 4))) return rc;
-        if ((rc = cl_grow(r, r->off, nb * 4))) return rc;
-        if ((rc = cl_grow(r, r->temp, exclusive_sum_temp_bytes((int)nb) + 256))) return rc;
+        if ((rc = rc_grow(c, "colour", r->flags, nb * 4))) return rc;
+        if ((rc = rc_grow(c, "colour", r->off, nb * 4))) return rc;
+        if ((rc = rc_grow(c, "colour", r->temp, exclusive_sum_temp_bytes((int)nb) + 256))) return rc;
     }
-    if (recent && (rc = cl_grow(r, r->cand, nb * 4))) return rc;
+    if (recent && (rc = rc_grow(c, "colour", r->cand, nb * 4))) return rc;
     if (select) {
-        if ((rc = cl_grow(r, r->cell, nb * 4))) return rc;
-        if ((rc = cl_grow(r, r->depth, nb * 8))) return rc;
-        if ((rc = cl_grow(r, r->sel, nb * 4))) return rc;
-        if ((rc = cl_grow(r, r->tab, (size_t)tab_n * 12))) return rc;
+        if ((rc = rc_grow(c, "colour", r->cell, nb * 4))) return rc;
+        if ((rc = rc_grow(c, "colour", r->depth, nb * 8))) return rc;
+        if ((rc = rc_grow(c, "colour", r->sel, nb * 4))) return rc;
+        if ((rc = rc_grow(c, "colour", r->tab, (size_t)tab_n * 12))) return rc;
     }
     hipStream_t s = r->s;
     ClCounters* cnt = (ClCounters*)r->small.p;
@@ -264,11 +239,8 @@ int immesh_colour_image(immesh_colourer* r, const immesh_image* im, int32_t mode
     if (model == IMMESH_COLOUR_PLAIN) cl_launch_dmin(s, cam, m.v_pos, d_sel, n_bound, cnt);
     if (n_bound > 0) cl_launch_update(s, cam, model, m.v_pos, d_sel, n_bound, cnt, (const uint8_t*)r->img.p, r->st, (float*)r->uv.p, (double*)r->partials.p);
     cl_launch_finalize(s, model, cnt, (const double*)r->partials.p, n_bound > 0 ? n_blocks : 0, d_stats);
-    HIPCHK(c, hipEventRecord(r->ev[3], s));
-    HIPCHK(c, hipMemcpyAsync(r->h_stats, d_stats, sizeof(immesh_colour_stats), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&r->ms[k], r->ev[k], r->ev[k + 1]);
+    if ((rc = rc_span_end(c, s, r->ev[2], r->ev[3], &r->ms[2], r->h_stats, d_stats, sizeof(immesh_colour_stats)))) return rc;
+    for (int k = 0; k < 2; k++) (void)hipEventElapsedTime(&r->ms[k], r->ev[k], r->ev[k + 1]);   // the three spans share that one synchronisation
     r->n_sel = r->h_stats->n_selected;
     r->d_sel = d_sel;
     r->sel_identity = d_sel == nullptr;
@@ -304,7 +276,7 @@ int immesh_colour_fetch(immesh_colourer* r, const int32_t* ids, int64_t n, uint8
     constexpr int64_t CL_FETCH_CHUNK = 1 << 16;
     const size_t b_ids = (size_t)CL_FETCH_CHUNK * 4, b_state = (size_t)CL_FETCH_CHUNK * sizeof(immesh_colour_state);
     int rc;
-    if ((rc = cl_grow(r, r->fetch, b_ids + b_state + (size_t)CL_FETCH_CHUNK * 3))) return rc;
+    if ((rc = rc_grow(c, "colour", r->fetch, b_ids + b_state + (size_t)CL_FETCH_CHUNK * 3))) return rc;
     char* d = (char*)r->fetch.p;
     hipStream_t s = r->s;
     for (int64_t i0 = 0; i0 < n; i0 += CL_FETCH_CHUNK) {

@@ -2,9 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <utility>
 #include <vector>
-#include "../../../include/immesh_closest.h"    // (and immesh_raycast.h): the frame and the distance statistics
+#include "rc_host.hpp"
+#include "../../../include/immesh_closest.h"   // (and immesh_raycast.h): the frame and the distance statistics
 #include "../../../include/immesh_topology.h"    // the stats the passes' records hold
 #include "../../../include/immesh_simplify.h"
 #include "../../../include/immesh_smooth.h"
@@ -76,38 +76,9 @@ void rc_launch_cast(hipStream_t s, const RcFrame& fr, const float* dirs, const f
 void rc_launch_points(hipStream_t s, const RcFrame& fr, const float* dirs, const float* origins, int64_t n_rays, float res, const float* t, float* pts,
                       float* cells, int32_t* keep);
 
-// ---- the host records: each releases what it holds when it is destroyed, so a buffer is freed by being a member --------------------------------------
-struct RcBuf {   // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-    RcBuf() = default;
-    RcBuf(const RcBuf&) = delete;
-    RcBuf& operator=(const RcBuf&) = delete;
-    ~RcBuf() { if (p) (void)hipFree(p); }
-};
-inline void rc_swap(RcBuf& a, RcBuf& b) {   // two buffers change places (an apply: a result becomes the snapshot)
-    std::swap(a.p, b.p);
-    std::swap(a.bytes, b.bytes);
-}
-inline void rc_destroy_events(hipEvent_t* e, int n) {
-    for (int i = 0; i < n; i++)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-}
-inline int rc_index_bits(int64_t n) {   // the bits the values 0 .. n - 1 need: the significant bits of a sort over them
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
-    return bits;
-}
-// grows b to at least `bytes` (contents are not kept); IMMESH_E_NOMEM with "<who>: hipMalloc(... B) failed" in the context
-int rc_grow(immesh_ctx* c, const char* who, RcBuf& b, size_t bytes);
-// checks a frame (twelve finite values; "<who>: frame rotation / position is not finite") and copies it
+// ---- the host records: RcBuf, the shared checks, the end of a span and the thinning tail are rc_host.hpp's (the renderer and the colourer use them too)
+// checks a frame (rc_finite_pose: "<who>: frame rotation / position is not finite") and copies it
 int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr);
-// dst = `bytes` of device memory, unless dst is NULL or nothing is asked for
-int rc_fetch(immesh_ctx* c, void* dst, const void* src, size_t bytes);
-// the room of a fetch.  rc_cap_negative: "<who>: cap is negative".  rc_cap: that check, then *n_out = n (when given) and, when an output is wanted,
-// "<who>: cap <cap> < <n> <noun>" (IMMESH_E_CAPACITY)
-int rc_cap_negative(immesh_ctx* c, const char* who, int64_t cap);
-int rc_cap(immesh_ctx* c, const char* who, int64_t cap, int64_t n, int64_t* n_out, bool wanted, const char* noun);
 
 // a hierarchy and the scratch of its build: the caster's over faces, the cloud index's over points
 struct RcTree {
@@ -295,7 +266,7 @@ struct immesh_raycaster {
     RcBuf vtx, faces;                                                              // the built snapshot
     RcTree tree;                                                                   // (its temp also serves the reinforce pass and the sampler)
     RcBuf dirs[2], org[2], t[2], face[2];                                          // the last cast of each mode ([0] NEAREST: the reinforce pass reads it)
-    RcBuf pts, cells, keep, koff, slot, tab, out, small;                           // reinforce
+    RcThin th;                                                                     // reinforce
     bool built = false;
     int64_t n_vtx = 0, n_faces = 0;
     // the last NEAREST cast, as the reinforce pass reads it
@@ -325,16 +296,6 @@ void rc_analysis_changed(immesh_raycaster* r);
 int rc_built(immesh_raycaster* r, const char* who);
 int rc_analysed(immesh_raycaster* r, const char* who);
 int rc_passed(immesh_raycaster* r, const char* who, const RcPass& p, const char* none);
-// the argument checks more than one entry point makes, each refusal with the caller's name in front: "<who>: <none>" unless `have`; "<who>: need 0 <
-// <what>, finite"; "<who>: bad point array" (n outside [0, RC_MAX_COUNT], or points without an array); "<who>: need <what> in [0, 2^31 - 2]"
-constexpr int64_t RC_MAX_COUNT = (int64_t)0x7FFFFFFE;
-int rc_have(immesh_ctx* c, const char* who, bool have, const char* none);
-int rc_positive(immesh_ctx* c, const char* who, const char* what, double v);
-int rc_points(immesh_ctx* c, const char* who, const float* pts, int64_t n);
-int rc_count_arg(immesh_ctx* c, const char* who, const char* what, int64_t v);
-// The end of a span on s: ev1 recorded, `bytes` of device memory copied to the pinned dst behind it (nothing when bytes == 0), the launches' error
-// checked, s idle, *ms = ev0 .. ev1.
-int rc_span_end(immesh_ctx* c, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, float* ms, void* dst = nullptr, const void* src = nullptr, size_t bytes = 0);
 // A pass on its owner's stream.  ready: the events and n_pinned pinned words if absent, the n_cnt device counters; the pass remembers c, s and `who`,
 // which prefixes the messages of this and every later rc_pass_grow.  begin: ev[e0] recorded, the counters zeroed.  end: rc_span_end over ev[e0],
 // ev[e1] and ms[span] with the counters [first, first + n) copied to h_cnt (n == 0: no copy).  span: an end without counters or error check (an

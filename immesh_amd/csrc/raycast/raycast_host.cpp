@@ -1,4 +1,4 @@
-// Host side of the ray caster (include/immesh_raycast.h): argument checks, grow-only buffers, the build and cast sequences on the caster's stream.
+// Host side of the ray caster (include/immesh_raycast.h): the shared scaffold of rc_host.hpp, argument checks, the build and cast sequences on the caster's stream.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -23,11 +23,17 @@ int rc_grow(immesh_ctx* c, const char* who, RcBuf& b, size_t bytes) {
     return 0;
 }
 
-int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr) {
+int rc_finite_pose(immesh_ctx* c, const char* who, const char* noun, const double rot[9], const double pos[3]) {
     for (int i = 0; i < 9; i++)
-        if (!std::isfinite(frame->rot[i])) { c->err = std::string(who) + ": frame rotation is not finite"; return IMMESH_E_INVAL; }
+        if (!std::isfinite(rot[i])) { c->err = std::string(who) + ": " + noun + " rotation is not finite"; return IMMESH_E_INVAL; }
     for (int i = 0; i < 3; i++)
-        if (!std::isfinite(frame->pos[i])) { c->err = std::string(who) + ": frame position is not finite"; return IMMESH_E_INVAL; }
+        if (!std::isfinite(pos[i])) { c->err = std::string(who) + ": " + noun + " position is not finite"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int rc_frame(immesh_ctx* c, const char* who, const immesh_ray_frame* frame, RcFrame* fr) {
+    const int rc = rc_finite_pose(c, who, "frame", frame->rot, frame->pos);
+    if (rc) return rc;
     std::memcpy(fr->rot, frame->rot, sizeof(fr->rot));
     std::memcpy(fr->pos, frame->pos, sizeof(fr->pos));
     return 0;
@@ -88,6 +94,30 @@ int rc_count_arg(immesh_ctx* c, const char* who, const char* what, int64_t v) {
     return 0;
 }
 
+int rc_check_soup(immesh_ctx* c, const char* who, int64_t max_faces, const float* vtx, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
+    if (n_vtx < 0 || n_faces < 0 || n_faces > max_faces || (n_vtx > 0 && !vtx) || (n_faces > 0 && !faces)) {
+        c->err = std::string(who) + ": bad vertex / face arrays";
+        return IMMESH_E_INVAL;
+    }
+    for (int64_t i = 0; i < 3 * n_faces; i++)
+        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
+            c->err = std::string(who) + ": face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
+                     std::to_string(n_vtx) + ")";
+            return IMMESH_E_INVAL;
+        }
+    return 0;
+}
+
+int rc_upload_soup(immesh_ctx* c, const char* who, hipStream_t s, RcBuf& d_vtx, RcBuf& d_faces, const float* vtx, int64_t n_vtx, const int32_t* faces,
+                   int64_t n_faces) {
+    int rc;
+    if ((rc = rc_grow(c, who, d_vtx, (size_t)n_vtx * 12))) return rc;
+    if ((rc = rc_grow(c, who, d_faces, (size_t)n_faces * 12))) return rc;
+    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(d_vtx.p, vtx, (size_t)n_vtx * 12, hipMemcpyHostToDevice, s));
+    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(d_faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
 int cx_built(immesh_cloud_index* x, const char* who) { return rc_have(x->ctx, who, x->built, "no index has been built (immesh_cloud_index_build)"); }
 
 int cx_caster(immesh_cloud_index* x, const immesh_raycaster* r, const char* who) {
@@ -107,6 +137,51 @@ int rc_span_end(immesh_ctx* c, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, fl
     HIPCHK(c, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(ms, ev0, ev1);
     return 0;
+}
+
+int rc_thin_grow(immesh_ctx* c, const char* who, RcThin& th, RcBuf& temp, int64_t n, float res, uint32_t* mask) {
+    int rc;
+    if ((rc = rc_grow(c, who, temp, rd_scan_temp_bytes(1, 1, n) + 256))) return rc;
+    if ((rc = rc_grow(c, who, th.pts, (size_t)n * 12))) return rc;
+    if ((rc = rc_grow(c, who, th.keep, (size_t)n * 4))) return rc;
+    if ((rc = rc_grow(c, who, th.koff, (size_t)n * 4))) return rc;
+    if ((rc = rc_grow(c, who, th.out, (size_t)n * 12))) return rc;
+    if ((rc = rc_grow(c, who, th.small, 16))) return rc;
+    *mask = 0;
+    if (res > 0.0f) {
+        uint64_t slots = 1024;
+        while (slots < 2 * (uint64_t)n) slots <<= 1;
+        *mask = (uint32_t)(slots - 1);
+        if ((rc = rc_grow(c, who, th.cells, (size_t)n * 12))) return rc;
+        if ((rc = rc_grow(c, who, th.slot, (size_t)n * 4))) return rc;
+        if ((rc = rc_grow(c, who, th.tab, (size_t)slots * 8))) return rc;
+    }
+    return 0;
+}
+
+int rc_thin_run(immesh_ctx* c, hipStream_t s, RcThin& th, RcBuf& temp, int64_t n, float res, uint32_t mask, const float* depth) {
+    int32_t* keep = (int32_t*)th.keep.p;
+    if (res > 0.0f) {
+        int32_t* tab_rep = (int32_t*)th.tab.p;
+        uint32_t* tab_min = (uint32_t*)(tab_rep + (size_t)mask + 1);
+        HIPCHK(c, hipMemsetAsync(tab_rep, 0xFF, ((size_t)mask + 1) * 8, s));   // rep -1, min 0xFFFFFFFF
+        rd_launch_hash_insert(s, n, depth, (const float*)th.cells.p, tab_rep, tab_min, mask, (uint32_t*)th.slot.p);
+        rd_launch_hash_keep(s, n, depth, tab_min, (const uint32_t*)th.slot.p, keep);
+    }
+    rd_scan_i32(s, temp.p, temp.bytes, keep, (int32_t*)th.koff.p, n);
+    rd_launch_compact(s, n, (const float*)th.pts.p, keep, (const int32_t*)th.koff.p, (float*)th.out.p, (int64_t*)th.small.p);
+    return 0;
+}
+
+int rc_thin_fetch(immesh_ctx* c, const char* who, const RcThin& th, int64_t n_points, float* xyz_out, int64_t cap, int64_t* n_out) {
+    if (n_out) *n_out = n_points;
+    if (!xyz_out || n_points == 0) return 0;
+    if (cap < n_points) {
+        c->err = std::string(who) + ": cap " + std::to_string(cap) + " < " + std::to_string(n_points) + " points";
+        return IMMESH_E_CAPACITY;
+    }
+    (void)hipSetDevice(c->cfg.device);
+    return rc_fetch(c, xyz_out, th.out.p, (size_t)n_points * 12);
 }
 
 int rc_pass_ready(immesh_ctx* c, hipStream_t s, const char* who, RcPass& p, int n_cnt, int n_pinned) {
@@ -203,26 +278,7 @@ int rc_tree_build(immesh_ctx* c, const char* who, hipStream_t s, hipEvent_t ev0,
     return 0;
 }
 
-namespace {
-
-constexpr int64_t RC_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;
-
-int rc_check_soup(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
-    immesh_ctx* c = r->ctx;
-    if (n_vtx < 0 || n_faces < 0 || n_faces > RC_MAX_FACES || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
-        c->err = "raycast_build_triangles: bad vertex / face arrays";
-        return IMMESH_E_INVAL;
-    }
-    for (int64_t i = 0; i < 3 * n_faces; i++)
-        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
-            c->err = "raycast_build_triangles: face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
-                     std::to_string(n_vtx) + ")";
-            return IMMESH_E_INVAL;
-        }
-    return 0;
-}
-
-}  // namespace
+static constexpr int64_t RC_MAX_FACES = (int64_t)1 << RC_INDEX_BITS;
 
 // What a change of the caster's state discards.  A change of the snapshot is a build (rc_build: a rebuild, and the applies of a holes pass, a
 // manifold pass, a simplification and a smoothing pass, which end in one) or the apply of an orientation, which keeps the hierarchy.  A new analysis replaces the old.
@@ -339,14 +395,12 @@ void immesh_raycaster_destroy(immesh_raycaster* r) {
 int immesh_raycast_build_triangles(immesh_raycaster* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
     if (!r) return IMMESH_E_INVAL;
     immesh_ctx* c = r->ctx;
-    int rc = rc_check_soup(r, vtx_xyz, n_vtx, faces, n_faces);   // before anything is touched: a refused soup leaves the built snapshot as it was
+    // before anything is touched: a refused soup leaves the built snapshot as it was
+    int rc = rc_check_soup(c, "raycast_build_triangles", RC_MAX_FACES, vtx_xyz, n_vtx, faces, n_faces);
     if (rc) return rc;
     (void)hipSetDevice(c->cfg.device);
     r->built = false;
-    if ((rc = rc_grow(c, "raycast", r->vtx, (size_t)n_vtx * 12))) return rc;
-    if ((rc = rc_grow(c, "raycast", r->faces, (size_t)n_faces * 12))) return rc;
-    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
-    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
+    if ((rc = rc_upload_soup(c, "raycast", r->s, r->vtx, r->faces, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     return rc_build(r, n_vtx, n_faces);
 }
 
@@ -423,46 +477,18 @@ int immesh_raycast_points(immesh_raycaster* r, double downsample_res, float* xyz
     r->n_points = 0;
     if (n > 0) {
         int rc;
-        if ((rc = rc_grow(c, "raycast", r->tree.temp, rd_scan_temp_bytes(1, 1, n) + 256))) return rc;
-        if ((rc = rc_grow(c, "raycast", r->pts, (size_t)n * 12))) return rc;
-        if ((rc = rc_grow(c, "raycast", r->keep, (size_t)n * 4))) return rc;
-        if ((rc = rc_grow(c, "raycast", r->koff, (size_t)n * 4))) return rc;
-        if ((rc = rc_grow(c, "raycast", r->out, (size_t)n * 12))) return rc;
-        if ((rc = rc_grow(c, "raycast", r->small, 16))) return rc;
         uint32_t mask = 0;
-        if (res > 0.0f) {
-            uint64_t tab = 1024;
-            while (tab < 2 * (uint64_t)n) tab <<= 1;
-            mask = (uint32_t)(tab - 1);
-            if ((rc = rc_grow(c, "raycast", r->cells, (size_t)n * 12))) return rc;
-            if ((rc = rc_grow(c, "raycast", r->slot, (size_t)n * 4))) return rc;
-            if ((rc = rc_grow(c, "raycast", r->tab, (size_t)tab * 8))) return rc;
-        }
-        const float* t = (const float*)r->t[0].p;
-        int32_t* keep = (int32_t*)r->keep.p;
+        RcThin& th = r->th;
+        if ((rc = rc_thin_grow(c, "raycast", th, r->tree.temp, n, res, &mask))) return rc;
+        const float* t = (const float*)r->t[0].p;   // the tail's depth array: -1 = no point
         HIPCHK(c, hipEventRecord(r->ev[4], s));
-        rc_launch_points(s, r->frame, (const float*)r->dirs[0].p, r->have_origins ? (const float*)r->org[0].p : nullptr, n, res, t, (float*)r->pts.p,
-                         (float*)r->cells.p, keep);
-        if (res > 0.0f) {   // the renderer's thinning, as it is: a count, a depth array (t: -1 = no point) and cells
-            int32_t* tab_rep = (int32_t*)r->tab.p;
-            uint32_t* tab_min = (uint32_t*)(tab_rep + (size_t)mask + 1);
-            HIPCHK(c, hipMemsetAsync(tab_rep, 0xFF, ((size_t)mask + 1) * 8, s));   // rep -1, min 0xFFFFFFFF
-            rd_launch_hash_insert(s, n, t, (const float*)r->cells.p, tab_rep, tab_min, mask, (uint32_t*)r->slot.p);
-            rd_launch_hash_keep(s, n, t, tab_min, (const uint32_t*)r->slot.p, keep);
-        }
-        rd_scan_i32(s, r->tree.temp.p, r->tree.temp.bytes, keep, (int32_t*)r->koff.p, n);
-        rd_launch_compact(s, n, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
-        if ((rc = rc_span_end(c, s, r->ev[4], r->ev[5], &r->ms[2], r->h_small + 1, r->small.p, 8))) return rc;
+        rc_launch_points(s, r->frame, (const float*)r->dirs[0].p, r->have_origins ? (const float*)r->org[0].p : nullptr, n, res, t, (float*)th.pts.p,
+                         (float*)th.cells.p, (int32_t*)th.keep.p);
+        if ((rc = rc_thin_run(c, s, th, r->tree.temp, n, res, mask, t))) return rc;
+        if ((rc = rc_span_end(c, s, r->ev[4], r->ev[5], &r->ms[2], r->h_small + 1, th.small.p, 8))) return rc;
         r->n_points = r->h_small[1];
     }
-    if (n_out) *n_out = r->n_points;
-    if (!xyz_out || r->n_points == 0) return 0;
-    if (cap < r->n_points) {
-        c->err = "raycast_points: cap " + std::to_string(cap) + " < " + std::to_string(r->n_points) + " points";
-        return IMMESH_E_CAPACITY;
-    }
-    HIPCHK(c, hipMemcpy(xyz_out, r->out.p, (size_t)r->n_points * 12, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_thin_fetch(c, "raycast_points", r->th, r->n_points, xyz_out, cap, n_out);
 }
 
 int immesh_raycaster_last_timing(immesh_raycaster* r, float ms[3]) {

@@ -7,12 +7,8 @@
 #include "../host_ctx.hpp"
 #include "../../../include/immesh_shade.h"
 #include "../colour/colour.hpp"
+#include "../raycast/rc_host.hpp"
 #include "render.hpp"
-
-struct RdBuf {   // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 
 struct immesh_renderer {
     immesh_ctx* ctx = nullptr;
@@ -20,8 +16,9 @@ struct immesh_renderer {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_shade[2] = {nullptr, nullptr};
     int64_t* h_small = nullptr;   // pinned: [0] pairs of the render, [1] reinforced points, [2] the colour pass's range (two floats)
-    RdBuf vtx, faces, rec, cnt, foff, temp, tiles, bins, depth, face, pts, cells, keep, koff, slot, tab, out, small;
-    RdBuf vrgb, vcol, rgb, srange;   // the colour pass: a soup's vertex bytes, packed vertex colours, the image, range keys + range + partials
+    RcBuf vtx, faces, rec, cnt, foff, temp, tiles, bins, depth, face;
+    RcThin th;                       // reinforce
+    RcBuf vrgb, vcol, rgb, srange;   // the colour pass: a soup's vertex bytes, packed vertex colours, the image, range keys + range + partials
     int64_t n_points = 0;
     float ms[2] = {0.0f, 0.0f};
     float shade_ms = 0.0f;
@@ -38,20 +35,7 @@ struct RdShadeJob {
 
 namespace {
 
-int rd_grow(immesh_renderer* r, RdBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return 0;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        r->ctx->err = "render: hipMalloc(" + std::to_string(want) + " B) failed";
-        return IMMESH_E_NOMEM;
-    }
-    b.bytes = want;
-    return 0;
-}
+constexpr int64_t RD_MAX_FACES = (int64_t)INT_MAX - 1;
 
 int rd_check_camera(immesh_renderer* r, const immesh_camera* cam) {
     if (!cam) { r->ctx->err = "render: camera is NULL"; return IMMESH_E_INVAL; }
@@ -64,36 +48,9 @@ int rd_check_camera(immesh_renderer* r, const immesh_camera* cam) {
         r->ctx->err = "render: need 0 < z_near < z_far, both finite";
         return IMMESH_E_INVAL;
     }
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(cam->rot[i])) { r->ctx->err = "render: camera rotation is not finite"; return IMMESH_E_INVAL; }
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(cam->pos[i])) { r->ctx->err = "render: camera position is not finite"; return IMMESH_E_INVAL; }
+    const int rc = rc_finite_pose(r->ctx, "render", "camera", cam->rot, cam->pos);
+    if (rc) return rc;
     if (std::isnan(cam->downsample_res)) { r->ctx->err = "render: downsample_res is NaN"; return IMMESH_E_INVAL; }
-    return 0;
-}
-
-int rd_check_soup(immesh_renderer* r, const char* who, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
-    immesh_ctx* c = r->ctx;
-    if (n_vtx < 0 || n_faces < 0 || n_faces >= (int64_t)INT_MAX || (n_vtx > 0 && !vtx_xyz) || (n_faces > 0 && !faces)) {
-        c->err = std::string(who) + ": bad vertex / face arrays";
-        return IMMESH_E_INVAL;
-    }
-    for (int64_t i = 0; i < 3 * n_faces; i++)
-        if (faces[i] < 0 || (int64_t)faces[i] >= n_vtx) {
-            c->err = std::string(who) + ": face " + std::to_string(i / 3) + " has vertex index " + std::to_string(faces[i]) + " out of range [0, " +
-                     std::to_string(n_vtx) + ")";
-            return IMMESH_E_INVAL;
-        }
-    return 0;
-}
-
-int rd_upload_soup(immesh_renderer* r, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces) {
-    immesh_ctx* c = r->ctx;
-    int rc;
-    if ((rc = rd_grow(r, r->vtx, (size_t)n_vtx * 12))) return rc;
-    if ((rc = rd_grow(r, r->faces, (size_t)n_faces * 12))) return rc;
-    if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vtx.p, vtx_xyz, (size_t)n_vtx * 12, hipMemcpyHostToDevice, r->s));
-    if (n_faces > 0) HIPCHK(c, hipMemcpyAsync(r->faces.p, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, r->s));
     return 0;
 }
 
@@ -136,31 +93,20 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
     const int64_t n_pix = (int64_t)rc.w * rc.h;
     const float res = (float)cam->downsample_res;
     int rc_ = 0;
-    if ((rc_ = rd_grow(r, r->rec, (size_t)n_faces * sizeof(RdFace)))) return rc_;
-    if ((rc_ = rd_grow(r, r->cnt, (size_t)n_faces * 8))) return rc_;
-    if ((rc_ = rd_grow(r, r->foff, (size_t)(n_faces + 1) * 8))) return rc_;
-    if ((rc_ = rd_grow(r, r->temp, rd_scan_temp_bytes(n_faces, n_tiles, n_pix) + 256))) return rc_;
-    if ((rc_ = rd_grow(r, r->tiles, (size_t)n_tiles * 12))) return rc_;
-    if ((rc_ = rd_grow(r, r->depth, (size_t)n_pix * 4))) return rc_;
-    if ((rc_ = rd_grow(r, r->face, (size_t)n_pix * 4))) return rc_;
-    if ((rc_ = rd_grow(r, r->pts, (size_t)n_pix * 12))) return rc_;
-    if ((rc_ = rd_grow(r, r->keep, (size_t)n_pix * 4))) return rc_;
-    if ((rc_ = rd_grow(r, r->koff, (size_t)n_pix * 4))) return rc_;
-    if ((rc_ = rd_grow(r, r->out, (size_t)n_pix * 12))) return rc_;
-    if ((rc_ = rd_grow(r, r->small, 16))) return rc_;
-    if (job) {
-        if ((rc_ = rd_grow(r, r->rgb, (size_t)n_pix * 3))) return rc_;
-        if ((rc_ = rd_grow(r, r->srange, 16 + 8 * (size_t)RD_SHADE_RANGE_PARTS))) return rc_;
-        if (job->sh.source != IMMESH_SHADE_WHITE && (rc_ = rd_grow(r, r->vcol, (size_t)n_vtx * 4))) return rc_;
-    }
+    if ((rc_ = rc_grow(c, "render", r->rec, (size_t)n_faces * sizeof(RdFace)))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->cnt, (size_t)n_faces * 8))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->foff, (size_t)(n_faces + 1) * 8))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->temp, rd_scan_temp_bytes(n_faces, n_tiles, n_pix) + 256))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->tiles, (size_t)n_tiles * 12))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->depth, (size_t)n_pix * 4))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->face, (size_t)n_pix * 4))) return rc_;
     uint32_t mask = 0;
-    if (res > 0.0f) {
-        uint64_t cap = 1024;
-        while (cap < 2 * (uint64_t)n_pix) cap <<= 1;
-        mask = (uint32_t)(cap - 1);
-        if ((rc_ = rd_grow(r, r->cells, (size_t)n_pix * 12))) return rc_;
-        if ((rc_ = rd_grow(r, r->slot, (size_t)n_pix * 4))) return rc_;
-        if ((rc_ = rd_grow(r, r->tab, (size_t)cap * 8))) return rc_;
+    RcThin& th = r->th;
+    if ((rc_ = rc_thin_grow(c, "render", th, r->temp, n_pix, res, &mask))) return rc_;
+    if (job) {
+        if ((rc_ = rc_grow(c, "render", r->rgb, (size_t)n_pix * 3))) return rc_;
+        if ((rc_ = rc_grow(c, "render", r->srange, 16 + 8 * (size_t)RD_SHADE_RANGE_PARTS))) return rc_;
+        if (job->sh.source != IMMESH_SHADE_WHITE && (rc_ = rc_grow(c, "render", r->vcol, (size_t)n_vtx * 4))) return rc_;
     }
     RdFace* rec = (RdFace*)r->rec.p;
     int64_t* cnt = (int64_t*)r->cnt.p;
@@ -182,7 +128,7 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
         c->err = "render: " + std::to_string(n_pairs) + " (face, tile) pairs in one render, more than 2^31 - 1";
         return IMMESH_E_CAPACITY;
     }
-    if ((rc_ = rd_grow(r, r->bins, (size_t)n_pairs * 4))) return rc_;
+    if ((rc_ = rc_grow(c, "render", r->bins, (size_t)n_pairs * 4))) return rc_;
     HIPCHK(c, hipMemsetAsync(tile_cnt, 0, (size_t)n_tiles * 12, s));
     rd_launch_bin(s, rc, rec, foff, n_faces, n_pairs, 0, tile_cnt, nullptr, nullptr, nullptr);
     rd_scan_i32(s, r->temp.p, r->temp.bytes, tile_cnt, tile_off, n_tiles);
@@ -191,24 +137,11 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
     HIPCHK(c, hipEventRecord(r->ev[1], s));
 
     // ---- reinforce
-    int32_t* keep = (int32_t*)r->keep.p;
-    rd_launch_unproject(s, rc, res, depth, (float*)r->pts.p, (float*)r->cells.p, keep);
-    if (res > 0.0f) {
-        int32_t* tab_rep = (int32_t*)r->tab.p;
-        uint32_t* tab_min = (uint32_t*)(tab_rep + (size_t)mask + 1);
-        HIPCHK(c, hipMemsetAsync(tab_rep, 0xFF, ((size_t)mask + 1) * 8, s));   // rep -1, min 0xFFFFFFFF
-        rd_launch_hash_insert(s, n_pix, depth, (const float*)r->cells.p, tab_rep, tab_min, mask, (uint32_t*)r->slot.p);
-        rd_launch_hash_keep(s, n_pix, depth, tab_min, (const uint32_t*)r->slot.p, keep);
-    }
-    rd_scan_i32(s, r->temp.p, r->temp.bytes, keep, (int32_t*)r->koff.p, n_pix);
-    rd_launch_compact(s, n_pix, (const float*)r->pts.p, keep, (const int32_t*)r->koff.p, (float*)r->out.p, (int64_t*)r->small.p);
-    HIPCHK(c, hipEventRecord(r->ev[2], s));
-    HIPCHK(c, hipMemcpyAsync(r->h_small + 1, r->small.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
+    rd_launch_unproject(s, rc, res, depth, (float*)th.pts.p, (float*)th.cells.p, (int32_t*)th.keep.p);
+    if ((rc_ = rc_thin_run(c, s, th, r->temp, n_pix, res, mask, depth))) return rc_;
+    if ((rc_ = rc_span_end(c, s, r->ev[1], r->ev[2], &r->ms[1], r->h_small + 1, th.small.p, 8))) return rc_;
     r->n_points = r->h_small[1];
-    (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);
-    (void)hipEventElapsedTime(&r->ms[1], r->ev[1], r->ev[2]);
+    (void)hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]);   // (complete since the synchronisation above)
 
     // ---- colour pass
     if (job) {
@@ -220,11 +153,7 @@ int rd_render(immesh_renderer* r, const immesh_camera* cam, const float* d_vtx, 
         if (axis && sh.range_from_vertices) rd_launch_shade_range(s, d_vtx, n_vtx, sh.axis, (uint32_t*)(range + 2), keys);
         if (sh.source != IMMESH_SHADE_WHITE) rd_launch_shade_colours(s, sh, d_vtx, n_vtx, job->d_bytes, job->st, keys, (uint32_t*)r->vcol.p, range);
         rd_launch_shade(s, rc, sh, rec, d_faces, face, sh.source == IMMESH_SHADE_WHITE ? nullptr : (const uint32_t*)r->vcol.p, (uint8_t*)r->rgb.p);
-        HIPCHK(c, hipEventRecord(r->ev_shade[1], s));
-        if (axis) HIPCHK(c, hipMemcpyAsync(r->h_small + 2, range, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(s));
-        (void)hipEventElapsedTime(&r->shade_ms, r->ev_shade[0], r->ev_shade[1]);
+        if ((rc_ = rc_span_end(c, s, r->ev_shade[0], r->ev_shade[1], &r->shade_ms, r->h_small + 2, range, axis ? 8 : 0))) return rc_;
         float lo_hi[2] = {0.0f, 0.0f};
         if (axis) std::memcpy(lo_hi, r->h_small + 2, 8);
         r->shade_lo_hi[0] = (double)lo_hi[0]; r->shade_lo_hi[1] = (double)lo_hi[1];
@@ -279,16 +208,11 @@ void immesh_renderer_destroy(immesh_renderer* r) {
     if (!r) return;
     (void)hipSetDevice(r->ctx->cfg.device);
     if (r->s) (void)hipStreamSynchronize(r->s);
-    for (RdBuf* b : {&r->vtx, &r->faces, &r->rec, &r->cnt, &r->foff, &r->temp, &r->tiles, &r->bins, &r->depth, &r->face, &r->pts, &r->cells, &r->keep,
-                     &r->koff, &r->slot, &r->tab, &r->out, &r->small, &r->vrgb, &r->vcol, &r->rgb, &r->srange})
-        if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : r->ev_shade)
-        if (e) (void)hipEventDestroy(e);
+    rc_destroy_events(r->ev, 3);
+    rc_destroy_events(r->ev_shade, 2);
     if (r->h_small) (void)hipHostFree(r->h_small);
     if (r->s) (void)hipStreamDestroy(r->s);
-    delete r;
+    delete r;   // the members release their buffers
 }
 
 int immesh_render_triangles(immesh_renderer* r, const immesh_camera* cam, const float* vtx_xyz, int64_t n_vtx, const int32_t* faces, int64_t n_faces,
@@ -297,9 +221,9 @@ int immesh_render_triangles(immesh_renderer* r, const immesh_camera* cam, const 
     immesh_ctx* c = r->ctx;
     int rc = rd_check_camera(r, cam);
     if (rc) return rc;
-    if ((rc = rd_check_soup(r, "render_triangles", vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    if ((rc = rc_check_soup(c, "render_triangles", RD_MAX_FACES, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     (void)hipSetDevice(c->cfg.device);
-    if ((rc = rd_upload_soup(r, vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    if ((rc = rc_upload_soup(c, "render", r->s, r->vtx, r->faces, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     return rd_render(r, cam, (const float*)r->vtx.p, n_vtx, (const int32_t*)r->faces.p, n_faces, depth_out, face_out);
 }
 
@@ -318,15 +242,7 @@ int immesh_render_mesh(immesh_renderer* r, const immesh_camera* cam, double smoo
 
 int immesh_render_points(immesh_renderer* r, float* xyz_out, int64_t cap, int64_t* n_out) {
     if (!r) return IMMESH_E_INVAL;
-    if (n_out) *n_out = r->n_points;
-    if (!xyz_out || r->n_points == 0) return 0;
-    if (cap < r->n_points) {
-        r->ctx->err = "render_points: cap " + std::to_string(cap) + " < " + std::to_string(r->n_points) + " points";
-        return IMMESH_E_CAPACITY;
-    }
-    (void)hipSetDevice(r->ctx->cfg.device);
-    HIPCHK(r->ctx, hipMemcpy(xyz_out, r->out.p, (size_t)r->n_points * 12, hipMemcpyDeviceToHost));
-    return 0;
+    return rc_thin_fetch(r->ctx, "render_points", r->th, r->n_points, xyz_out, cap, n_out);
 }
 
 int immesh_renderer_last_timing(immesh_renderer* r, float ms[2]) {
@@ -352,13 +268,13 @@ int immesh_shade_triangles(immesh_renderer* r, const immesh_camera* cam, const f
     if (rc) return rc;
     RdShadeJob job;
     if ((rc = rd_check_shade(r, sh, &job))) return rc;
-    if ((rc = rd_check_soup(r, "shade_triangles", vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    if ((rc = rc_check_soup(c, "shade_triangles", RD_MAX_FACES, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     const bool bytes = sh->source == IMMESH_SHADE_VERTEX;
     if (bytes && !vtx_rgb) { c->err = "shade_triangles: source VERTEX without vertex colours"; return IMMESH_E_INVAL; }
     (void)hipSetDevice(c->cfg.device);
-    if ((rc = rd_upload_soup(r, vtx_xyz, n_vtx, faces, n_faces))) return rc;
+    if ((rc = rc_upload_soup(c, "render", r->s, r->vtx, r->faces, vtx_xyz, n_vtx, faces, n_faces))) return rc;
     if (bytes) {
-        if ((rc = rd_grow(r, r->vrgb, (size_t)n_vtx * 3))) return rc;
+        if ((rc = rc_grow(c, "render", r->vrgb, (size_t)n_vtx * 3))) return rc;
         if (n_vtx > 0) HIPCHK(c, hipMemcpyAsync(r->vrgb.p, vtx_rgb, (size_t)n_vtx * 3, hipMemcpyHostToDevice, r->s));
         job.d_bytes = (const uint8_t*)r->vrgb.p;
     }
