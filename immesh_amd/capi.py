@@ -988,6 +988,53 @@ class HotPath:
         f = self.lib.immesh_align_set_variant; f.argtypes = [C.c_void_p, C.c_int32]; f.restype = C.c_int
         self._check(f(self.raycaster(), variant), "align_set_variant")
 
+    # -- align a cloud to the indexed cloud (include/immesh_align.h, the Cloud rule) ---------------------------------------------------------------------
+    def align_cloud_step(self, pts, opts, huber=0.0, frame=None, want_index=False, want_terms=False):
+        """immesh_align_cloud_step: one step at `frame` (None: world coordinates) against the index's cloud -> (AlignSystem, index (n,) int32 or None,
+        terms (n, 28) float64 or None)"""
+        f = self.lib.immesh_align_cloud_step
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.POINTER(AlignOptions), C.c_double, C.POINTER(AlignSystem), C.c_void_p,
+                      C.c_void_p]
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        index = np.empty(len(p), np.int32) if want_index else None
+        terms = np.empty((len(p), ALIGN_TERMS), np.float64) if want_terms else None
+        sy = AlignSystem()
+        self._check(f(self.cloud_index(), None if frame is None else C.byref(frame), _ptr(p), len(p), None if opts is None else C.byref(opts), huber,
+                      C.byref(sy), _ptr(index), _ptr(terms)), "align_cloud_step")
+        return sy, index, terms
+
+    def align_cloud(self, pts, opts=None, huber=0.0, frame=None, centre=None, history_cap=None, **over):
+        """immesh_align_cloud: the loop from `frame` (None: the identity) against the index's cloud -> (AlignResult, history (iterations, 4) float64:
+        n_used, rms, |omega|, |v|).  opts, centre and history_cap as align()'s."""
+        f = self.lib.immesh_align_cloud
+        f.argtypes = [C.c_void_p, C.POINTER(RayFrame), C.c_void_p, C.c_int64, C.POINTER(AlignOptions), C.c_double, C.POINTER(AlignResult), C.c_void_p,
+                      C.c_int64]
+        f.restype = C.c_int
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        o = align_options(**over) if opts is None else opts
+        if centre is not None:
+            o = AlignOptions.from_buffer_copy(o)
+            o.centre[:] = align_centre_mean(p, frame) if isinstance(centre, str) and centre == "mean" else [float(x) for x in centre]
+        cap = max(0, min(int(o.max_iters), 10000)) if history_cap is None else history_cap
+        hist = np.zeros((max(cap, 0), 4), np.float64)
+        res = AlignResult()
+        self._check(f(self.cloud_index(), None if frame is None else C.byref(frame), _ptr(p), len(p), C.byref(o), huber, C.byref(res), _ptr(hist), cap),
+                    "align_cloud")
+        return res, hist[:min(res.iterations, max(cap, 0))]
+
+    def align_cloud_timing(self):
+        """device milliseconds of (the last step, the sum over the last loop's steps) of the Cloud rule"""
+        f = self.lib.immesh_align_cloud_last_timing; f.argtypes = [C.c_void_p, C.c_void_p]; f.restype = C.c_int
+        ms = (C.c_float * 2)()
+        self._check(f(self.cloud_index(), ms), "align_cloud_last_timing")
+        return float(ms[0]), float(ms[1])
+
+    def align_cloud_set_variant(self, variant):
+        """immesh_align_cloud_set_variant: 0 the fused step, 1 split (the default, by measurement); for measurements: the same bits"""
+        f = self.lib.immesh_align_cloud_set_variant; f.argtypes = [C.c_void_p, C.c_int32]; f.restype = C.c_int
+        self._check(f(self.cloud_index(), variant), "align_cloud_set_variant")
+
     # -- mesh-to-cloud distances (include/immesh_nearest.h) ------------------------------------------------------------------------------------------
     def cloud_index(self):
         """the context's cloud index (created at first use, destroyed by close())"""

@@ -12,14 +12,12 @@ static_assert(sizeof(immesh_align_options) == 64, "immesh_align_options layout")
 static_assert(sizeof(immesh_align_system) == sizeof(AlSystemDev), "the folded system is copied as it lies");
 static_assert(sizeof(immesh_align_result) == 368, "immesh_align_result layout");
 
-namespace {
-
-int al_h_index(int a, int b) { return a * (13 - a) / 2 + (b - a); }   // a <= b
-
 bool al_nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
 
+// ---- shared with the cloud rule (align_cloud_host.cpp): align.hpp declares them -----------------------------------------------------------------------
 // the checks a step makes of its options: what it reads
-int al_check_step(immesh_ctx* c, const std::string& who, const immesh_align_options* o) {
+int al_check_step(immesh_ctx* c, const char* who_, const immesh_align_options* o) {
+    const std::string who = who_;
     if (!o) { c->err = who + ": options are NULL"; return IMMESH_E_INVAL; }
     if (const int rc = rc_positive(c, who.c_str(), "max_dist", o->max_dist)) return rc;
     if (o->mode != IMMESH_ALIGN_POINT && o->mode != IMMESH_ALIGN_PLANE) { c->err = who + ": mode " + std::to_string(o->mode) + " is neither 0 (POINT) nor 1 (PLANE)"; return IMMESH_E_INVAL; }
@@ -27,6 +25,81 @@ int al_check_step(immesh_ctx* c, const std::string& who, const immesh_align_opti
         if (!std::isfinite(o->centre[k])) { c->err = who + ": centre is not finite"; return IMMESH_E_INVAL; }
     return 0;
 }
+
+// what the loop reads of its options besides
+int al_check_loop(immesh_ctx* c, const char* who_, const immesh_align_options* opts) {
+    const std::string who = who_;
+    if (!al_nonneg_finite(opts->damping)) { c->err = who + ": need damping >= 0, finite"; return IMMESH_E_INVAL; }
+    if (opts->max_iters < 1 || opts->max_iters > 10000) { c->err = who + ": max_iters " + std::to_string(opts->max_iters) + " outside [1, 10000]"; return IMMESH_E_INVAL; }
+    if (!al_nonneg_finite(opts->eps_rot) || !al_nonneg_finite(opts->eps_trans)) { c->err = who + ": need eps_rot and eps_trans >= 0, finite"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+int al_check_loop_out(immesh_ctx* c, const char* who_, const immesh_align_result* result_out, const double* history_out, int64_t history_cap) {
+    const std::string who = who_;
+    if (!result_out) { c->err = who + ": result_out is NULL"; return IMMESH_E_INVAL; }
+    if (history_cap < 0 || (history_cap > 0 && !history_out)) { c->err = who + ": bad history array"; return IMMESH_E_INVAL; }
+    return 0;
+}
+
+void al_identity(RcFrame* fr) {
+    *fr = RcFrame{};
+    fr->rot[0] = fr->rot[4] = fr->rot[8] = 1.0;
+}
+
+// The Loop rule of the header, for both rules: the statements between two steps stand here and nowhere else.
+int al_loop(const immesh_align_options& o, const RcFrame& fr0, AlStepFn step, void* self, float* total_ms, immesh_align_result* result_out,
+            double* history_out, int64_t history_cap) {
+    int rc;
+    RcFrame fr = fr0;
+    immesh_ray_frame frame;
+    std::memcpy(frame.rot, fr.rot, sizeof fr.rot);
+    std::memcpy(frame.pos, fr.pos, sizeof fr.pos);
+    const int64_t need = o.mode == IMMESH_ALIGN_PLANE ? 6 : 3;
+    immesh_align_result res = {};
+    res.status = IMMESH_ALIGN_MAX_ITERS;
+    float total = 0.0f;
+    for (int it = 0; it < o.max_iters; it++) {
+        std::memcpy(fr.rot, frame.rot, sizeof fr.rot);
+        std::memcpy(fr.pos, frame.pos, sizeof fr.pos);
+        float ms = 0.0f;
+        if ((rc = step(self, fr, &res.system, &ms))) return rc;
+        total += ms;
+        res.iterations = it + 1;
+        const int64_t rows = o.mode == IMMESH_ALIGN_PLANE ? res.system.n_used : 3 * res.system.n_used;
+        res.rms = rows > 0 ? std::sqrt(res.system.e / (double)rows) : 0.0;
+        double delta[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, nw = 0.0, nv = 0.0;
+        bool stop = false;
+        if (res.system.n_used < need) {
+            res.status = IMMESH_ALIGN_TOO_FEW;
+            stop = true;
+        } else if (immesh_align_solve(&res.system, o.damping, delta) != 0) {
+            res.status = IMMESH_ALIGN_DEGENERATE;
+            stop = true;
+        } else {
+            (void)immesh_align_update(&frame, o.centre, delta, &frame);
+            nw = std::sqrt((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2]);
+            nv = std::sqrt((delta[3] * delta[3] + delta[4] * delta[4]) + delta[5] * delta[5]);
+            if (nw <= o.eps_rot && nv <= o.eps_trans) {
+                res.status = IMMESH_ALIGN_CONVERGED;
+                stop = true;
+            }
+        }
+        if (it < history_cap) {
+            double* h = history_out + 4 * (size_t)it;
+            h[0] = (double)res.system.n_used; h[1] = res.rms; h[2] = nw; h[3] = nv;
+        }
+        if (stop) break;
+    }
+    *total_ms = total;
+    res.frame = frame;
+    *result_out = res;
+    return 0;
+}
+
+namespace {
+
+int al_h_index(int a, int b) { return a * (13 - a) / 2 + (b - a); }   // a <= b
 
 int al_check_points(immesh_ctx* c, const std::string& who, const float* pts, int64_t n_pts) {
     return rc_points(c, who.c_str(), pts, n_pts);
@@ -77,9 +150,17 @@ int al_step(immesh_raycaster* r, const RcFrame& fr, int has_frame, int64_t n_pts
     return 0;
 }
 
-void al_identity(RcFrame* fr) {
-    *fr = RcFrame{};
-    fr->rot[0] = fr->rot[4] = fr->rot[8] = 1.0;
+// the loop's step on the caster: the uploaded cloud under a frame, nothing stored per point
+struct AlMeshLoop {
+    immesh_raycaster* r;
+    int64_t n_pts;
+    const immesh_align_options* opts;
+};
+int al_mesh_step(void* self, const RcFrame& fr, immesh_align_system* sys, float* ms) {
+    const AlMeshLoop& l = *(const AlMeshLoop*)self;
+    const int rc = al_step(l.r, fr, 1, l.n_pts, *l.opts, sys, nullptr, nullptr);
+    *ms = l.r->al.ms[0];
+    return rc;
 }
 
 }  // namespace
@@ -193,58 +274,15 @@ int immesh_align(immesh_raycaster* r, const immesh_ray_frame* frame0, const floa
     int rc;
     if ((rc = rc_built(r, "align"))) return rc;
     if ((rc = al_check_step(c, "align", opts))) return rc;
-    if (!al_nonneg_finite(opts->damping)) { c->err = "align: need damping >= 0, finite"; return IMMESH_E_INVAL; }
-    if (opts->max_iters < 1 || opts->max_iters > 10000) { c->err = "align: max_iters " + std::to_string(opts->max_iters) + " outside [1, 10000]"; return IMMESH_E_INVAL; }
-    if (!al_nonneg_finite(opts->eps_rot) || !al_nonneg_finite(opts->eps_trans)) { c->err = "align: need eps_rot and eps_trans >= 0, finite"; return IMMESH_E_INVAL; }
+    if ((rc = al_check_loop(c, "align", opts))) return rc;
     if ((rc = al_check_points(c, "align", pts, n_pts))) return rc;
-    if (!result_out) { c->err = "align: result_out is NULL"; return IMMESH_E_INVAL; }
-    if (history_cap < 0 || (history_cap > 0 && !history_out)) { c->err = "align: bad history array"; return IMMESH_E_INVAL; }
+    if ((rc = al_check_loop_out(c, "align", result_out, history_out, history_cap))) return rc;
     RcFrame fr;
     al_identity(&fr);
     if (frame0 && (rc = rc_frame(c, "align", frame0, &fr))) return rc;
     if ((rc = al_upload(r, pts, n_pts))) return rc;
-    immesh_ray_frame frame;
-    std::memcpy(frame.rot, fr.rot, sizeof fr.rot);
-    std::memcpy(frame.pos, fr.pos, sizeof fr.pos);
-    const int64_t need = opts->mode == IMMESH_ALIGN_PLANE ? 6 : 3;
-    immesh_align_result res = {};
-    res.status = IMMESH_ALIGN_MAX_ITERS;
-    float total = 0.0f;
-    for (int it = 0; it < opts->max_iters; it++) {
-        std::memcpy(fr.rot, frame.rot, sizeof fr.rot);
-        std::memcpy(fr.pos, frame.pos, sizeof fr.pos);
-        if ((rc = al_step(r, fr, 1, n_pts, *opts, &res.system, nullptr, nullptr))) return rc;
-        total += al.ms[0];
-        res.iterations = it + 1;
-        const int64_t rows = opts->mode == IMMESH_ALIGN_PLANE ? res.system.n_used : 3 * res.system.n_used;
-        res.rms = rows > 0 ? std::sqrt(res.system.e / (double)rows) : 0.0;
-        double delta[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, nw = 0.0, nv = 0.0;
-        bool stop = false;
-        if (res.system.n_used < need) {
-            res.status = IMMESH_ALIGN_TOO_FEW;
-            stop = true;
-        } else if (immesh_align_solve(&res.system, opts->damping, delta) != 0) {
-            res.status = IMMESH_ALIGN_DEGENERATE;
-            stop = true;
-        } else {
-            (void)immesh_align_update(&frame, opts->centre, delta, &frame);
-            nw = std::sqrt((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2]);
-            nv = std::sqrt((delta[3] * delta[3] + delta[4] * delta[4]) + delta[5] * delta[5]);
-            if (nw <= opts->eps_rot && nv <= opts->eps_trans) {
-                res.status = IMMESH_ALIGN_CONVERGED;
-                stop = true;
-            }
-        }
-        if (it < history_cap) {
-            double* h = history_out + 4 * (size_t)it;
-            h[0] = (double)res.system.n_used; h[1] = res.rms; h[2] = nw; h[3] = nv;
-        }
-        if (stop) break;
-    }
-    al.ms[1] = total;
-    res.frame = frame;
-    *result_out = res;
-    return 0;
+    AlMeshLoop self = {r, n_pts, opts};
+    return al_loop(*opts, fr, al_mesh_step, &self, &al.ms[1], result_out, history_out, history_cap);
 }
 
 int immesh_align_last_timing(immesh_raycaster* r, float ms[2]) {

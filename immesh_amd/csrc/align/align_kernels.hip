@@ -8,16 +8,9 @@
 //   split     the same step in two launches (the walk stores face and q, the second forms and folds the terms): kept for the measurement, as is
 //             the fused kernel without its register cap (immesh_align_set_variant; tools/align_bench.py)
 // Double arithmetic is written in the contract's order; the library builds with -ffp-contract=off, so nothing is fused.
-#include "align.hpp"
-#include "../raycast/raycast_dev.hpp"
+#include "align_dev.hpp"   // al_row, al_block_fold: the cloud-to-cloud step (align_cloud_kernels.hip) shares them
 
 namespace {
-
-constexpr int AL_BLOCK = RC_BLOCK;
-constexpr int AL_WAVES = AL_BLOCK / 64;
-static_assert(AL_WAVES == 4, "the fold adds four wavefront partials in index order");
-
-struct AlCentre { double c[3]; };
 
 // the walk's leaf: D of a face by the closest query's Face rule; of the face that was accepted last, its q
 struct AlFaceLeaf {
@@ -34,28 +27,6 @@ struct AlFaceLeaf {
     }
     __device__ __forceinline__ void accept() { best_q[0] = q[0]; best_q[1] = q[1]; best_q[2] = q[2]; }
 };
-
-// one row (j, r), j = (cross(x, u), u), added to the terms (first: the row that begins the sums)
-__device__ __forceinline__ void al_row(const double* x, const double* u, double r, bool first, double* t) {
-    double j[6];
-    rc_cross(x, u, j);
-    j[3] = u[0]; j[4] = u[1]; j[5] = u[2];
-    int idx = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int b = a; b < 6; b++, idx++) {
-            const double v = j[a] * j[b];
-            t[idx] = first ? v : t[idx] + v;
-        }
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-        const double v = j[a] * r;
-        t[21 + a] = first ? v : t[21 + a] + v;
-    }
-    const double rr = r * r;
-    t[27] = first ? rr : t[27] + rr;
-}
 
 // the terms of a point with a winner; false: PLANE mode and a flat winner (t is left as it was)
 __device__ __forceinline__ bool al_terms(int mode, const double* p, const AlCentre& ce, const double* q, const float* __restrict__ vtx,
@@ -82,37 +53,6 @@ __device__ __forceinline__ bool al_terms(int mode, const double* p, const AlCent
     const double u[3] = {n[0] / s, n[1] / s, n[2] / s};
     al_row(x, u, rc_dot(u, A[0]), true, t);
     return true;
-}
-
-// The workgroup's fold of (t, c) -> out[0], written by lanes 0 .. 31.  Every lane of the workgroup calls it.
-__device__ __forceinline__ void al_block_fold(double* t, long long* c, AlSystemDev* out) {
-    __shared__ double s_t[AL_WAVES][AL_TERMS];
-    __shared__ long long s_c[AL_WAVES][4];
-#pragma unroll
-    for (int k = 0; k < AL_TERMS; k++) {
-        double v = t[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        t[k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        long long v = c[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        c[k] = v;
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < AL_TERMS; k++) s_t[w][k] = t[k];
-#pragma unroll
-        for (int k = 0; k < 4; k++) s_c[w][k] = c[k];
-    }
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < AL_TERMS) out->s[k] = ((s_t[0][k] + s_t[1][k]) + s_t[2][k]) + s_t[3][k];
-    else if (k < AL_TERMS + 4) out->n[k - AL_TERMS] = ((s_c[0][k - AL_TERMS] + s_c[1][k - AL_TERMS]) + s_c[2][k - AL_TERMS]) + s_c[3][k - AL_TERMS];
 }
 
 // what follows the walk of point i: its terms and counts, the per-point outputs, the workgroup's partial
@@ -228,11 +168,11 @@ __global__ void __launch_bounds__(AL_BLOCK) al_fold_kernel(const AlSystemDev* __
     al_block_fold(t, c, res);
 }
 
-AlCentre al_centre(const double* c) { return AlCentre{{c[0], c[1], c[2]}}; }
-
 }  // namespace
 
 int64_t al_blocks(int64_t n_pts) { return (n_pts + AL_BLOCK - 1) / AL_BLOCK; }
+
+void al_launch_fold(hipStream_t s, const AlSystemDev* part, int64_t n_part, AlSystemDev* res) { al_fold_kernel<<<1, AL_BLOCK, 0, s>>>(part, n_part, res); }
 
 void al_launch_step(hipStream_t s, bool capped, const RcFrame& fr, int has_frame, const float* pts, int64_t n_pts, double r2, int mode, const double* centre,
                     const float* vtx, const int32_t* faces, const RcNode* nodes, int64_t n_in, AlSystemDev* part, AlSystemDev* res, int32_t* face_out,
@@ -244,7 +184,7 @@ void al_launch_step(hipStream_t s, bool capped, const RcFrame& fr, int has_frame
     else if (blocks > 0)
         al_step_kernel<<<(unsigned)blocks, AL_BLOCK, 0, s>>>(fr, has_frame, pts, n_pts, r2, mode, al_centre(centre), vtx, faces, nodes, n_in, part, face_out,
                                                              terms_out);
-    al_fold_kernel<<<1, AL_BLOCK, 0, s>>>(part, blocks, res);
+    al_launch_fold(s, part, blocks, res);
 }
 
 void al_launch_step_split(hipStream_t s, const RcFrame& fr, int has_frame, const float* pts, int64_t n_pts, double r2, int mode, const double* centre,
@@ -256,5 +196,5 @@ void al_launch_step_split(hipStream_t s, const RcFrame& fr, int has_frame, const
         al_terms_kernel<<<(unsigned)blocks, AL_BLOCK, 0, s>>>(fr, has_frame, pts, n_pts, mode, al_centre(centre), vtx, faces, sface, sq, part, face_out,
                                                               terms_out);
     }
-    al_fold_kernel<<<1, AL_BLOCK, 0, s>>>(part, blocks, res);
+    al_launch_fold(s, part, blocks, res);
 }

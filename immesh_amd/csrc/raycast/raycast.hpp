@@ -157,8 +157,8 @@ struct RcSample {
     }
 };
 
-// What the seven passes over the snapshot share (analysis, orientation, holes, manifold, simplification, smoothing, self-intersections), and the three
-// rules of the cloud index (neighbours, normals, clusters): the events of their spans, the device counters and their pinned copy, all created by
+// What the seven passes over the snapshot share (analysis, orientation, holes, manifold, simplification, smoothing, self-intersections), and the four
+// rules of the cloud index (neighbours, normals, clusters, alignment): the events of their spans, the device counters and their pinned copy, all created by
 // rc_pass_ready at the pass' first call and never before, on the owner's context and stream; `have`: a result of the current snapshot (of the current
 // analysis, for the orientation, the holes and the manifold pass; of the index's current cloud) exists.  rc_snapshot_changed / rc_analysis_changed and
 // cx_cloud_changed / cx_normals_changed below clear it.
@@ -358,6 +358,16 @@ struct RcNormals : RcPass {                                    // spans: normals
     int64_t n = 0;                                             // the cloud's size when the normals were made
 };
 
+// alignment of a cloud to the index's cloud (include/immesh_align.h, the Cloud rule; align/align_cloud_host.cpp): allocated at the first step, never
+// before.  It keeps nothing that a later call reads: every call uploads its source cloud and answers from its own launches, so a change of the
+// index's cloud has nothing of it to discard.
+struct RcCloudAlign : RcPass {                                 // span: a step; ms[1]: the sum over the last loop; cnt / h_cnt: the folded system (32 words) and its pinned copy
+    RcBuf pts, part;                                           // the source cloud; per-workgroup partials
+    RcBuf index, terms;                                        // per point, only when asked for
+    RcBuf sindex, sq;                                          // the split variant's winner and q per point
+    int variant = 1;                                           // 0 fused (registers capped), 1 split: the default, by measurement
+};
+
 // An index over a point cloud: the caster's hierarchy with a point as a box whose lo == hi, built by the same rc_tree_build, one point per leaf.
 struct immesh_cloud_index {
     immesh_ctx* ctx = nullptr;
@@ -376,6 +386,7 @@ struct immesh_cloud_index {
     RcKnn kn;
     RcNormals nr;
     RcClusters cl;
+    RcCloudAlign ca;
 };
 // the index's discard rule (its table stands above them in raycast_host.cpp): what was made on the cloud, and what read the normals
 void cx_cloud_changed(immesh_cloud_index* x);

@@ -55,6 +55,32 @@
  * Validated before any launch: a built caster; a finite frame when one is given, a finite centre; 0 < max_dist finite; mode 0 or 1; damping >= 0
  * finite; 1 <= max_iters <= 10000; eps_rot, eps_trans >= 0 finite; n_pts in [0, 2^31 - 2]; else IMMESH_E_INVAL with text in immesh_last_error(ctx).
  * immesh_align_step checks what it reads: the caster, the frame, the centre, max_dist, mode and the points.
+ *
+ * ---- Cloud rule: align a cloud to the indexed cloud (nearest-point least squares) ---------------------------------------------------------------------
+ * The target is the cloud of an immesh_cloud_index (the mesh-to-cloud header's, the one that declares immesh_nearest_points; named here by its tag
+ * alone, and that header is not included), not a mesh: scan-to-scan registration, a sweep placed in a survey cloud, an alignment before any mesh
+ * exists.  All arithmetic is IEEE double, in the order written, no fused multiply-add.  The Point, Cloud, D, Winner and Box rules are those of the
+ * mesh-to-cloud header, with r2 = max_dist max_dist.  Reference point, Rows, Terms, System, Solve, Exp, Update and Loop are the rules above, word for
+ * word, except where stated here.
+ *   Correspondence: p = the source point under the current frame (Point rule).  The winner is the cloud point c_j with the smallest D; on equal D
+ *            the smaller index wins.  q_k = (double)c_j,k - p_k: these are the e_k of the D rule, so D is (q_x q_x + q_y q_y) + q_z q_z bit for bit.
+ *            A point without a winner is counted n_no_face (read here: no neighbour), one that fails the Point rule n_not_finite; neither contributes.
+ *   POINT rows: as above: three rows j = (cross(x, e_k), e_k), r = q_k.  On a caster built from the target as a soup of degenerate faces (i, i, i) the
+ *            mesh rule's Face rule returns the corner, its q is this q and its D this D (the Box bound of a point's own box is D), so in POINT mode
+ *            with huber == 0 the two rules give the same terms and the same system, bit for bit.
+ *   PLANE rows: one row.  It needs the index's stored normals (immesh_cloud_normals, made since the index's last build or apply); without them the
+ *            call is IMMESH_E_INVAL with text, before any launch.  A winner whose normal status is not 0 is counted n_flat (read here: a winner
+ *            without a normal) and the point contributes nothing.  Else u_a = the stored float normal widened to double -- it is not renormalised:
+ *            |u| is 1 within float rounding --, j = (cross(x, u), u), r = (u_x q_x + u_y q_y) + u_z q_z.
+ *            Negating u negates j and r exactly (every product and sum of cross and of r changes its sign and nothing else), and the 28 terms are
+ *            products of two of them: they do not depend on the sign mode the normals were made with.
+ *   Weight:  huber >= 0, finite.  huber == 0: the terms are as above.  huber > 0: d = sqrt(D) (POINT), d = |r| (PLANE); w = 1.0 when d <= huber, else
+ *            w = huber / d; each of the 28 terms t becomes w t.  The rms of the Loop rule is then the weighted one: sqrt of the weighted e over the
+ *            rows.
+ *   Loop:    as above: TOO_FEW below 3 (POINT) / 6 (PLANE) used points.  An empty index gives TOO_FEW; that is not an error.
+ * Validated before any launch: what immesh_align checks (a built index in the caster's place), huber, and in PLANE mode the normals; else
+ * IMMESH_E_INVAL with text.  A refused call leaves the index as it was, and a call that succeeds leaves the index's query results, neighbour results,
+ * masks, clusters and normals byte for byte as they were.
  */
 #ifndef IMMESH_ALIGN_H
 #define IMMESH_ALIGN_H
@@ -118,6 +144,25 @@ int immesh_align_last_timing(immesh_raycaster* rc, float ms[2]);
  * the walk's occupancy), 1 the split step -- the walk stores face and q per point, a second launch forms and folds the terms --, 2 the fused step
  * without the register cap.  All give the same bits; DESIGN section 26 has their figures. */
 int immesh_align_set_variant(immesh_raycaster* rc, int32_t variant);
+
+/* ---- the Cloud rule: the same options, system and result, their layouts unchanged ---- */
+struct immesh_cloud_index;     /* the cloud index of the mesh-to-cloud header (its typedef immesh_cloud_index names the same type) */
+
+/* One step at `frame` (NULL: the points are world coordinates) against the index's cloud.  It reads mode, max_dist and centre of opts.  index_out
+ * (n_pts int32: the winner, -1 without one) and terms_out (n_pts x 28 doubles) may each be NULL; when both are NULL nothing is stored per point.
+ * Nothing is allocated or launched for this rule before its first call; the buffers are grow-only and the launches run on the index's stream. */
+int immesh_align_cloud_step(struct immesh_cloud_index* ix, const immesh_ray_frame* frame, const float* pts, int64_t n_pts,
+                            const immesh_align_options* opts, double huber, immesh_align_system* system_out, int32_t* index_out, double* terms_out);
+/* The Loop rule over that step, with immesh_align_solve and immesh_align_update.  history_out as immesh_align's. */
+int immesh_align_cloud(struct immesh_cloud_index* ix, const immesh_ray_frame* frame0, const float* pts, int64_t n_pts, const immesh_align_options* opts,
+                       double huber, immesh_align_result* result_out, double* history_out, int64_t history_cap);
+/* Device time in milliseconds from HIP events on the index's stream: [0] the last step  [1] the sum over the last loop's steps (the last step's
+ * after an immesh_align_cloud_step).  The copy of the points to the device is not included. */
+int immesh_align_cloud_last_timing(struct immesh_cloud_index* ix, float ms[2]);
+/* For measurements (tools/align_cloud_bench.py): 0 the fused step, one launch whose registers are held to the walk's occupancy; 1 the split step --
+ * the walk stores winner and q per point, a second launch forms and folds the terms.  Both give the same bits.  The default is 1: measured, the fused
+ * step is level with the split one up to 100 000 points and 11 % slower at 1 000 000. */
+int immesh_align_cloud_set_variant(struct immesh_cloud_index* ix, int32_t variant);
 
 #ifdef __cplusplus
 }
